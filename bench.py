@@ -19,6 +19,12 @@ inside every step.
 --workload c4 (BASELINE.json configs[3], not the metric's line): SPE10 3520 x 1200 Q1 quads on [0,5]x[0,1]
 with 8 x 8 subdomains (block numbering), strong scaling -- rank r of N owns subdomains [64 r / N, 64 (r+1) / N)
 (columns of the 8 x 8 layout) and assembles its rows; same halo exchange.
+
+A plain run (--gpus / --steps / --warmup) sets up, warms up, times the steps and prints the JSON line; the roofline
+fields derived from the timed steps and from the build-stamped profile files stay in it.  --full adds the side
+measurements that take runs of their own (attainable-bandwidth probe before the warmup, CPU oracle baseline after the
+timed steps); without it `roofline.attainable`, `roofline.frac_of_torch_copy` and `cpu_baseline` are null.
+--dump-outputs DIR writes the last timed step's value arrays (a fixed seeded sample when large) as DIR/*.npy.
 """
 import argparse
 import json
@@ -45,8 +51,16 @@ def parse():
                          "(BASELINE.json configs[3]), strong scaling")
     ap.add_argument("--nx", type=int, default=0, help="c2: squares per strip in x per rank (3200); c4: 3520")
     ap.add_argument("--ny", type=int, default=0, help="c2: 640; c4: 1200")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target CPU work of the baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements that take runs of their own: the attainable-bandwidth probe "
+                         "(roofline.attainable, frac_of_torch_copy) and the CPU oracle baseline (cpu_baseline).  A "
+                         "plain run sets up, warms up, times the steps and prints the line with those fields null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step assembled as DIR/<name>.npy (float64; a "
+                         "fixed seeded sample of the value array where it exceeds the size budget)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0,
+                    help="--full: target CPU work of the baseline sample")
     ap.add_argument("--traffic-json", default=os.path.join(ROOT, "profiles", "r06", "traffic.json"),
                     help="PMC traffic summary (scripts/traffic_summary.py); used only when its build_id matches the "
                          "timed libhdd_amd.so")
@@ -59,7 +73,7 @@ def parse():
                     help="N>1: exchange the halo before the whole assembly instead of overlapping it "
                          "with the interior tiles")
     ap.add_argument("--probe-last", action="store_true",
-                    help="run the attainable-bandwidth probe after the timed steps (default: before the warmup)")
+                    help="--full: run the attainable-bandwidth probe after the timed steps (default: before the warmup)")
     ap.add_argument("--halo", default="step", choices=["step", "once"],
                     help="N>1: exchange the face halo in every step (default) or once at setup -- the mesh and "
                          "the coefficients are static, so a re-assembly needs no exchange (SURVEY.md 8(e))")
@@ -159,6 +173,25 @@ def lib_build_id():
         return None
 
 
+DUMP_BUDGET_BYTES = 48 << 20   # all ranks and arrays of one --dump-outputs directory together
+
+
+def dump_outputs(torch, dirname, vals, world, rank):
+    """--dump-outputs: the value arrays the last timed step assembled (what a caller of the step receives), one
+    float64 .npy per array and rank.  An array above its share of DUMP_BUDGET_BYTES is written as a sample: the
+    entries at sorted indices drawn once from a fixed seed, so two builds run with the same arguments write the
+    same entries of the same inputs' matrix and can be compared file by file."""
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 8 // (world * len(vals))
+    for q, v in enumerate(vals):
+        n = v.numel()
+        if n > share:
+            idx = np.sort(np.random.default_rng([2014, q, rank]).integers(0, n, size=share))
+            v = v[torch.from_numpy(idx).to(v.device)]
+        name = "stiffness_values_%d%s.npy" % (q, "_rank%d" % rank if world > 1 else "")
+        np.save(os.path.join(dirname, name), v.cpu().numpy().astype(np.float64, copy=False))
+
+
 def main():
     args = parse()
     import torch
@@ -249,7 +282,8 @@ def main():
     # warmup on every rank: sustained HBM streaming on MI355X goes through a power-management transient
     # (C2 launches 11-30 of a back-to-back run take 225-260 us, before and after 200-215 us:
     # profiles/r02/s3/long/), and with the probe first the timed steps sit nearer the steady state.
-    att = None if args.probe_last else attainable_hbm(torch)
+    # The probe is a measurement of its own: only a --full run makes it.
+    att = attainable_hbm(torch) if args.full and not args.probe_last else None
     # the first step fills the ghost columns (NaN until then); --halo once keeps them for the timed steps
     step()
     gpu_sync("the first step")
@@ -306,6 +340,8 @@ def main():
     elapsed, kernel_ms_max = float(t[0]), float(t[1])
     if not np.isfinite(vals[0][:1024].cpu().numpy()).all():
         raise SystemExit("non-finite values: a ghost column was not filled by the halo")
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, vals, world, rank)
     total_dofs = nbf * grid.ne if c4 else dofs_rank * world
     value = total_dofs * args.steps / elapsed
 
@@ -375,10 +411,10 @@ def main():
             overlapped = not args.no_overlap and not c4
             halo_desc = ", %s face halo%s" % ("RCCL" if args.backend == "nccl" else "gloo host-staged (rehearsal)",
                                               " overlapped with the tiles" if overlapped else ", then every tile")
-        if att is None:
+        if att is None and args.full:
             att = attainable_hbm(torch)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline(nx // world, ny, args.cpu_seconds, cube=c4)
         out = {
             "metric": "assembled DoFs/sec (global stiffness), SPE10 SWIPDG p=1",
@@ -387,6 +423,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": 1e3 * elapsed / args.steps,
             "higher_is_better": True,
             "scaling": "strong" if c4 else "weak",
@@ -427,9 +464,9 @@ def main():
                          "frac_rocprof": (alg_bytes / (rocprof_ms * 1e-3) / 1e9 / HBM_PEAK_GBS) if rocprof_ms else None,
                          "algorithmic_bytes_per_launch": alg_bytes,
                          "algorithmic_bytes_all_ranks": all_bytes,
-                         # measured on this box in this run: device copy (read + write) and fill (write)
-                         "attainable": dict(att, source="torch copy_ / fill_ of 1 GiB, HIP events"),
-                         "frac_of_torch_copy": achieved / att["copy_gbs"],
+                         # --full, measured on the same device in this run: device copy (read + write) and fill (write)
+                         "attainable": dict(att, source="torch copy_ / fill_ of 1 GiB, HIP events") if att else None,
+                         "frac_of_torch_copy": achieved / att["copy_gbs"] if att else None,
                          "frac_note": "frac = SURVEY 8(d) algorithmic bytes (element-major coordinates, 48 B per "
                                       "triangle) / kernel time; traffic_frac = PMC-measured HBM bytes of this build "
                                       "(the vertex-indexed layout reads less) / kernel time, the physical rate"},
