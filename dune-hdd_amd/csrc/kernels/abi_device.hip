@@ -65,7 +65,7 @@ static hipError_t ctx_workspace(hdd_ctx* ctx, size_t bytes, void** out)
 
 using hdd::set_error;
 
-// vertex-indexed geometry is read with 32-bit byte offsets (swipdg_device.hh rsrc32): every [rows][n_local] int32 /
+// vertex-indexed geometry is read with 32-bit byte offsets (swipdg_elements.hh rsrc32): every [rows][n_local] int32 /
 // f64 row offset and every vertex row (at most 3 n_local vertices of 16 B) must stay below 2^32
 static bool vx_offsets_fit(int64_t n_local) { return n_local >= 0 && n_local * 48 < (int64_t(1) << 32); }
 

@@ -1,6 +1,7 @@
 // dune-hdd_amd/csrc/kernels/swipdg_assemble.hip -- dispatch of the SWIPDG stiffness / product kernels
-// (swipdg_device.hh) and the wave-per-row fallback kernels for the remaining quadrature rules.
-#include "swipdg_device.hh"
+// (the per-family entry points of swipdg_kernels.hh) and the wave-per-row fallback kernels for the remaining
+// quadrature rules.
+#include "swipdg_wave_per_row.hh"
 
 namespace hdd {
 namespace dev {
@@ -20,10 +21,7 @@ static hipError_t launch_components(const AssembleArgs& a, int nqv, int nqf, hip
     if (same) return launch_p1_smooth_fused(a, s);
   }
   for (int c = 0; c < a.n_comp; ++c) {
-    AssembleArgs ac = a;
-    ac.n_comp = 1;
-    ac.kappa[0] = a.kappa[c];
-    ac.vals[0] = a.vals[c];
+    const AssembleArgs ac = component_args(a, c);
     const bool smooth = smooth_kind(ac.kappa[0].kind);
     hipError_t e = hipSuccess;
     if (ac.elem_type == HDD_SIMPLEX && nqv == 1 && nqf == 2 && !smooth) e = launch_p1_pwc(ac, s);

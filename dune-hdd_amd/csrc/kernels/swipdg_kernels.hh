@@ -47,6 +47,27 @@ struct AssembleArgs {
   KappaArg kappa[HDD_MAX_COMP];
   double* vals[HDD_MAX_COMP];
 };
+// the arguments of component c alone: the kernels take one component per launch (kinds are compile-time in them)
+inline AssembleArgs component_args(const AssembleArgs& a, int c)
+{
+  AssembleArgs ac = a;
+  ac.n_comp = 1;
+  ac.kappa[0] = a.kappa[c];
+  ac.vals[0] = a.vals[c];
+  return ac;
+}
+// launch(args) once per component on that component's arguments; ALL_IN_ONE (policies that emit every component
+// per tile): once, on the arguments as they are
+template <bool ALL_IN_ONE, class F>
+hipError_t per_component(const AssembleArgs& a, F&& launch)
+{
+  for (int c = 0; c < (ALL_IN_ONE ? 1 : a.n_comp); ++c) {
+    launch(ALL_IN_ONE ? a : component_args(a, c));
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
 
 // ---------------------------------------------------------------------------------------------
 // Q_p on affine hexahedra (HDD_HEX): 1D reference tables of the tensor-product basis / quadrature
@@ -170,6 +191,15 @@ hipError_t launch_product_fast(const AssembleArgs& a, int product, hipStream_t s
 // the sharded Q1 step's value-major side buffers (list_elements == 4) into place (swipdg_q1.hip): a.tile_list /
 // n_tile_list = the listed elements, a.elem_ptr / nbrs / finfo / n_local / own_begin / n_cu
 hipError_t launch_q1_scatter_soa(const AssembleArgs& a, const double* buf, int64_t ld, double* vals, hipStream_t s);
+// per-family entry points of the persistent tile driver (one translation unit each)
+hipError_t launch_p1_pwc(const AssembleArgs& a, hipStream_t s);       // swipdg_p1.hip
+hipError_t launch_p1_smooth(const AssembleArgs& a, hipStream_t s);
+hipError_t launch_p1_penalty(const AssembleArgs& a, hipStream_t s);
+hipError_t launch_p1_smooth_fused(const AssembleArgs& a, hipStream_t s);   // all components in one launch
+hipError_t launch_q1_pwc(const AssembleArgs& a, hipStream_t s);       // swipdg_q1.hip
+hipError_t launch_q1_smooth(const AssembleArgs& a, hipStream_t s);
+hipError_t launch_q1_penalty(const AssembleArgs& a, hipStream_t s);
+hipError_t launch_vol_products(const AssembleArgs& a, int product, hipStream_t s);   // swipdg_vol.hip
 
 }  // namespace dev
 }  // namespace hdd

@@ -1,10 +1,15 @@
 // dune-hdd_amd/csrc/kernels/swipdg_q1.hip -- Q1 (parallelograms) instantiations of the persistent tile driver:
 // closed-form piecewise-constant stiffness (the C1 / C4 kernel), the smooth-kappa quadrature policy, the
 // SWIPDG penalty product.
-#include "swipdg_device.hh"
+#include "swipdg_policy_generic.hh"
+#include "swipdg_launch.hh"
 
 namespace hdd {
 namespace dev {
+
+template <int TK, int KK, bool VX> using Q1Pwc = Q1PwcPolicy<TK, KK, false, VX>;
+template <int TK, int KK, bool VX> using Q1PwcH2 = Q1PwcPolicy<TK, KK, false, VX, true>;
+template <int TK, int KK, bool VX> using Q1Smooth3 = GenericPolicy<Cube, 4, 3, TK, KK, VX>;
 
 // The C1 / C4 kernel.  With the mesh's vertex-indexed geometry: the half-image kernel (two waves per SIMD, 20 KB
 // image; round 5: every element computed once at full width, swapped between the wave's halves) -- the two waves

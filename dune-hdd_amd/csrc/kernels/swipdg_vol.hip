@@ -1,6 +1,7 @@
 // dune-hdd_amd/csrc/kernels/swipdg_vol.hip -- element-local products (l2, h1_semi, elliptic, boundary_l2) of
 // P1 / Q1 meshes with piecewise-constant data on the persistent tile driver (VolProductPolicy).
-#include "swipdg_device.hh"
+#include "swipdg_policy_generic.hh"
+#include "swipdg_launch.hh"
 
 namespace hdd {
 namespace dev {
@@ -11,15 +12,9 @@ static hipError_t launch_vol_product_vx(const AssembleArgs& a, hipStream_t s)
   if constexpr (KIND != HDD_PRODUCT_ELLIPTIC) {
     return launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_CONST, HDD_FN_CONST, VX>>(a, s);
   } else {
-    const bool pe = a.kappa[0].kind == HDD_FN_PER_ELEM;
-    if (a.tkind == HDD_TENSOR_CONST)
-      return pe ? launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_CONST, HDD_FN_PER_ELEM, VX>>(a, s)
-                : launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_CONST, HDD_FN_CONST, VX>>(a, s);
-    if (a.tkind == HDD_TENSOR_ISO_PER_ELEM)
-      return pe ? launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_ISO_PER_ELEM, HDD_FN_PER_ELEM, VX>>(a, s)
-                : launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_ISO_PER_ELEM, HDD_FN_CONST, VX>>(a, s);
-    return pe ? launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_SYM_PER_ELEM, HDD_FN_PER_ELEM, VX>>(a, s)
-              : launch_persistent<VolProductPolicy<E, KIND, HDD_TENSOR_SYM_PER_ELEM, HDD_FN_CONST, VX>>(a, s);
+    return with_pwc_kinds(a, [&](auto tk, auto kk) {
+      return launch_persistent<VolProductPolicy<E, KIND, tk.value, kk.value, VX>>(a, s);
+    });
   }
 }
 

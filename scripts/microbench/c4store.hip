@@ -2,7 +2,7 @@
 // (SPE10 3520 x 1200 Q1, 8 x 8 subdomains, subdomain-major element order, AllDirichlet: 337,768,960 values =
 // 2.70 GB), written in CSR order by tiles of 64 consecutive elements, under the organisations a kernel could use:
 //
-//   half20   per-wave 20 KB half images (32 row blocks), 2 waves per SIMD: today's Q1 kernel (swipdg_device.hh HALF)
+//   half20   per-wave 20 KB half images (32 row blocks), 2 waves per SIMD: today's Q1 kernel (swipdg_persistent.hh, the HALF branch)
 //   whole40  per-wave 40 KB whole-tile images, 1 wave per SIMD (round-1..3 Q1 kernel)
 //   coopW_T  a workgroup of W waves owns T adjacent tiles (T x 40 KB image); after a barrier all W waves stream the
 //            joint CSR range in 1 KB chunks interleaved over the waves (store k of thread i at 16 (i + 64 W k))

@@ -19,6 +19,9 @@ import hdd_amd as H  # noqa: E402
 
 
 def main():
+    if "abl" not in os.path.basename(H.LIB_PATH):   # (as bench_configs.py c5) a release library would ignore every value
+        sys.exit("sweep_wgcu.py: HDD_P1_WGCU is read by the ablation library only -- make -C dune-hdd_amd ablation, "
+                 "then run with HDD_AMD_LIB=dune-hdd_amd/lib_ab/libhdd_abl.so (loaded: %s)" % H.LIB_PATH)
     args = sys.argv[1:]
     wl = args.pop(0) if args and args[0] in ("c2", "c3", "c4") else "c4"
     values = [int(v) for v in args] or [4, 5, 6, 7, 8]

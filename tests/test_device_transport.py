@@ -53,6 +53,15 @@ def _layout(kind, n):
         return H.Grid.structured(H.SIMPLEX, 40 * n, 18, LOWER, UPPER, px=2 * n, py=2), H.TENSOR_SYM_PER_ELEM, True
     if kind == "q1_smooth":   # Q1 with a smooth (sinusoid) diffusion factor: the quadrature policy, no closed form
         return H.Grid.structured(H.CUBE, 48 * n, 30, LOWER, UPPER, px=2 * n, py=3), H.TENSOR_ISO_PER_ELEM, "smooth"
+    # column strips two elements wide: every owned element of the middle rank (every second one of an end rank) has a
+    # ghost face neighbour, so a 64-element tile of the in-place schedule's SKIP launch holds far more skipped
+    # elements than the 4 whose ranges the store stage keeps in scalar registers; no tile is uniform (each holds a
+    # boundary row), so the contiguous-image stores with their per-chunk tests run (P1: the 8-byte halves of mixed
+    # chunks of the odd 3 x 3 blocks)
+    if kind == "q1_narrow":
+        return H.Grid.structured(H.CUBE, 2 * n, 64, LOWER, UPPER, px=n, py=1), H.TENSOR_ISO_PER_ELEM, True
+    if kind == "p1_narrow":
+        return H.Grid.structured(H.SIMPLEX, 2 * n, 32, LOWER, UPPER, px=n, py=1), H.TENSOR_ISO_PER_ELEM, False
     raise ValueError(kind)
 
 
@@ -150,9 +159,13 @@ def run_device_ranks(grid, n, tk, two, schedules, steps=3, flags_extra=0):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,n", [("c2_p1", 2), ("c2_p1", 3), ("c4_q1", 2), ("c4_q1", 3), ("p1_sym", 3),
-                                    ("q1_smooth", 3)])
+                                    ("q1_smooth", 3), ("q1_narrow", 3), ("p1_narrow", 3)])
 def test_device_transport_equals_single_gpu(kind, n):
     grid, tk, two = _layout(kind, n)
+    if kind.endswith("_narrow"):   # what these layouts are for: more than 4 skipped elements in one tile, every rank
+        for r in range(n):   # (one subdomain per rank: rank r's local mesh is that of subdomain r)
+            ghost_adjacent = H.halo_elements(grid.local(r, r + 1))   # the predicate of the kernel's skip mask
+            assert np.bincount(ghost_adjacent // 64).max() >= 5, (r, ghost_adjacent)
     got, infos = run_device_ranks(grid, n, tk, two, SCHEDULES)
     peers = [i.n_peers for i in infos]
     assert peers == ([1, 1] if n == 2 else [1, 2, 1]), peers          # n = 3: the middle rank has two peers

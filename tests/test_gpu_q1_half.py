@@ -2,7 +2,7 @@
 LDS image, two waves per SIMD; the default on vertex-indexed meshes) == the whole-tile image kernel, bit for bit,
 on vertex-indexed and on element-major geometry.
 
-The two kernels run the same closed-form arithmetic (swipdg_device.hh, Q1PwcPolicy::compute) and differ only in
+The two kernels run the same closed-form arithmetic (swipdg_policy_generic.hh, Q1PwcPolicy::compute) and differ only in
 how a tile's row blocks reach HBM, so every value must be identical -- uniform, non-uniform and ragged tiles,
 tile lists, the sharded step's SKIP launch, Neumann / Dirichlet, iso / symmetric tensors, per-element kappa.
 The whole-tile kernel is itself pinned to the oracle (test_gpu_parity.py); the half-image kernel is checked
