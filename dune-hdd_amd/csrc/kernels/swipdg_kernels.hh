@@ -19,6 +19,15 @@ struct KappaArg {
 // smooth (evaluated at quadrature points) diffusion-factor kinds
 __host__ __device__ constexpr bool smooth_kind(int k) { return k == HDD_FN_SINUSOID || k == HDD_FN_FLATTOP; }
 
+// AssembleArgs::list_elements: what tile_list holds and where the values go
+enum : int32_t {
+  LIST_TILES = 0,         // 64-element tiles (or no list: every tile)
+  LIST_ELEMENTS = 1,      // single owned elements (relative to own_begin), row blocks in place through the LDS
+  LIST_SIDE_BUFFER = 2,   // the same without LDS, row blocks into side buffers vals[c] of fix_rb doubles per element
+  LIST_IN_PLACE = 3,      // the same, in place (beside a skip_ghost assembly)
+  LIST_SIDE_SOA = 4       // the same, into value-major side buffers of leading dimension fix_ld (Q1)
+};
+
 struct AssembleArgs {
   int32_t elem_type, n_comp;
   int64_t n_local, own_begin, own_end;
@@ -35,11 +44,9 @@ struct AssembleArgs {
   int32_t pad_v;
   const int32_t* tile_list;    // optional: 64-element tiles to assemble (relative to own_begin)
   int64_t n_tile_list;         // entries of tile_list (tile_list == nullptr: all tiles)
-  int32_t list_elements;       // 1: tile_list holds single owned elements (relative to own_begin), not tiles;
-                               // 2: the same, row blocks into side buffers vals[c] of fix_rb doubles per element;
-                               // 3: the same, in place without LDS (beside a skip_ghost assembly)
+  int32_t list_elements;       // LIST_*: tile_list holds tiles, or single owned elements (the element-list passes)
   int32_t fix_rb;
-  int64_t fix_ld;              // list_elements == 4: leading dimension of the value-major side buffers
+  int64_t fix_ld;              // LIST_SIDE_SOA: leading dimension of the value-major side buffers
   int32_t skip_ghost;          // 1: tiles do not store the row blocks of elements with a ghost face neighbour
   int32_t reserve_wg;          // skip_ghost launches: workgroup slots left free for the concurrent element pass
   const int32_t* ev;           // optional vertex-indexed geometry: element -> local vertex ids [nvpe][n_local]
@@ -117,7 +124,7 @@ void hex_q3g_reference_tables(const HexTables& t, double* out);
 // degree p in 1..3; (nq1v, nq1f) Gauss points per direction; *supported = false if no kernel matches
 hipError_t launch_hex(const HexArgs& a, int degree, int nq1v, int nq1f, hipStream_t s, bool* supported);
 
-// device pattern (any element type): blocks per element = 1 + interior faces
+// device pattern (pattern.hip; any element type): blocks per element = 1 + interior faces
 hipError_t launch_pattern_counts(const int32_t* nbrs, int32_t nf, int64_t n_local, int64_t own_begin, int64_t own_end,
                                  int64_t nb2, int64_t* d_counts, hipStream_t s);
 // elem_ptr [n_own + 1] (exclusive prefix of the row-block sizes) in two launches (three with scan_launch or
@@ -188,7 +195,7 @@ hipError_t launch_assemble(const AssembleArgs& a, int nqv, int nqf, hipStream_t 
 // products of P1 / Q1 meshes with piecewise-constant kappa on the persistent tile driver (closed forms);
 // *supported = false: use launch_product
 hipError_t launch_product_fast(const AssembleArgs& a, int product, hipStream_t s, bool* supported);
-// the sharded Q1 step's value-major side buffers (list_elements == 4) into place (swipdg_q1.hip): a.tile_list /
+// the sharded Q1 step's value-major side buffers (LIST_SIDE_SOA) into place (swipdg_q1.hip): a.tile_list /
 // n_tile_list = the listed elements, a.elem_ptr / nbrs / finfo / n_local / own_begin / n_cu
 hipError_t launch_q1_scatter_soa(const AssembleArgs& a, const double* buf, int64_t ld, double* vals, hipStream_t s);
 // per-family entry points of the persistent tile driver (one translation unit each)

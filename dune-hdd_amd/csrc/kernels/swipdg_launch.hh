@@ -56,12 +56,12 @@ static hipError_t launch_persistent(const AssembleArgs& a, hipStream_t s)
   const bool reserve = a.reserve_wg > 0 && !HDD_ABL(a, 4194304);
   if (reserve) slots = std::max<int64_t>(8, (slots - a.reserve_wg) & ~int64_t(7));
   const int64_t G = std::min<int64_t>(tiles, slots);
-  if (a.list_elements) {   // element-list fixup pass: one lane per element
+  if (a.list_elements != LIST_TILES) {   // element-list fixup pass: one lane per element
     const size_t lds_e = size_t(64) * P::RB * sizeof(double);
     const int64_t ge = std::min<int64_t>((a.n_tile_list + 63) / 64, int64_t(cus) * 4);
-    if (a.list_elements >= 2) {   // no LDS: into the side buffers (2: slot RB doubles) or in place (3)
-      if (a.list_elements == 2 && a.fix_rb != P::RB) return hipErrorInvalidValue;
-      if (a.list_elements == 4 && (!P::EMIT || a.fix_ld < a.n_tile_list + 1)) return hipErrorInvalidValue;
+    if (a.list_elements >= LIST_SIDE_BUFFER) {   // no LDS: into the side buffers (slot RB doubles) or in place
+      if (a.list_elements == LIST_SIDE_BUFFER && a.fix_rb != P::RB) return hipErrorInvalidValue;
+      if (a.list_elements == LIST_SIDE_SOA && (!P::EMIT || a.fix_ld < a.n_tile_list + 1)) return hipErrorInvalidValue;
       return per_component<P::FUSED>(a, [&](const AssembleArgs& ac) {
         hipLaunchKernelGGL((swipdg_elements_buf_kernel<P>), dim3(unsigned(ge)), dim3(64), 0, s, ac, a.n_tile_list);
       });

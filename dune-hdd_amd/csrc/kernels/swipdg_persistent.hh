@@ -705,9 +705,9 @@ __global__ void __launch_bounds__(64) swipdg_elements_kernel(const AssembleArgs 
 }
 
 // Element-list pass without LDS, so that it runs on the transfer stream beside a persistent assembly that holds
-// the LDS (sharded step, shard.hip).  a.list_elements == 3: lane i writes the row block of listed element i in
+// the LDS (sharded step, shard.hip).  LIST_IN_PLACE: lane i writes the row block of listed element i in
 // place (the concurrent assembly runs with a.skip_ghost and leaves those blocks alone; inactive lanes repeat
-// lane 0's element); == 2: into side buffers a.vals[c] + i RB (slot n: the inactive lanes' dummy), which
+// lane 0's element); LIST_SIDE_BUFFER: into side buffers a.vals[c] + i RB (slot n: the inactive lanes' dummy), which
 // fix_scatter_kernel copies into place after the join (round-3 A/B variant).
 template <class P>
 __global__ void __launch_bounds__(64) swipdg_elements_buf_kernel(const AssembleArgs a, int64_t n)
@@ -726,7 +726,7 @@ __global__ void __launch_bounds__(64) swipdg_elements_buf_kernel(const AssembleA
     P::load_gat(a, e, own, gat);
     P::load_gat2(a, gat);
     if constexpr (P::EMIT) {
-      if (a.list_elements == 4) {   // value-major side buffer: canonical value k of list entry i at vals[0][k fix_ld + i]
+      if (a.list_elements == LIST_SIDE_SOA) {   // value-major side buffer: canonical value k of list entry i at vals[0][k fix_ld + i]
         double* const buf = a.vals[0] + i;
         P::emit(a, own, gat, [&](int b, const double (&blk)[P::NB][P::NB]) {
           if (!act) return;
@@ -741,7 +741,7 @@ __global__ void __launch_bounds__(64) swipdg_elements_buf_kernel(const AssembleA
     [[maybe_unused]] typename P::Shared shv;
     if constexpr (FUSED) P::prepare(a, own, shv);
     const int ncomp = FUSED ? a.n_comp : 1;
-    const int64_t dst = a.list_elements == 3 ? a.elem_ptr[e - a.own_begin] : slot * RB;
+    const int64_t dst = a.list_elements == LIST_IN_PLACE ?a.elem_ptr[e - a.own_begin] : slot * RB;
     for (int c = 0; c < ncomp; ++c) {
       double* img = a.vals[c] + dst;
       if constexpr (FUSED) P::emit_component(a, c, e, own, gat, shv, img);

@@ -28,7 +28,7 @@ hipError_t launch_q1_smooth(const AssembleArgs& a, hipStream_t s) { return dispa
 
 // The sharded Q1 step's side buffer into place (after the join): one wave per listed element writes the element's
 // CSR row block contiguously (lane = CSR position), fetching each value from the value-major buffer the element
-// pass wrote in canonical order (list_elements == 4: value k = row i, block b, column c at k fix_ld + list entry).
+// pass wrote in canonical order (LIST_SIDE_SOA: value k = row i, block b, column c at k fix_ld + list entry).
 // The inverse of the block placement -- which canonical (b, c) a CSR position holds -- is recomputed from the
 // element's neighbour ids and face info (Q1PwcPolicy::positions / role_slot).
 __global__ void __launch_bounds__(64) fix_scatter_q1_kernel(const double* __restrict__ buf, int64_t ld,

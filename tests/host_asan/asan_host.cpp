@@ -1,7 +1,7 @@
 // Host-side sanitizer driver (AddressSanitizer + UndefinedBehaviorSanitizer) for the product's host code: the
 // grid providers, rank-local views, halo plans, coefficient lookups, CSR pattern builders and block-operator maps
 // of csrc/host/grid.cpp, called through the C ABI (include/hdd.h) over a sweep of sizes, partitions, element types,
-// boundary kinds and the documented error paths.  GPU code is out of reach of the sanitizers on this pool; this
+// boundary kinds and the documented error paths; and the quadrature rules of csrc/host/quadrature.cpp.  GPU code is out of reach of the sanitizers on this pool; this
 // covers everything the library runs on the host.  Built and run by tests/test_host_sanitizers.py.
 #include <cmath>
 #include <cstdio>
@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "hdd.h"
+#include "quadrature.hh"
 
 static int failures = 0;
 #define CHECK(cond)                                                            \
@@ -160,8 +161,108 @@ static void exercise_grid(hdd_grid* g, int32_t world)
   }
 }
 
+// Quadrature rules and Lagrange tables (csrc/host/quadrature.cpp) against closed forms.  Tolerance 1e-13, relative
+// for the moments and absolute for the Lagrange sums: about 30 times the worst errors measured for these checks
+// (g++ -O2 and hipcc -O3 with and without the library's floating-point flags agreed): Gauss-Legendre 3.3e-15,
+// simplex 1.8e-15, tensor 2.0e-15 (relative), Lagrange partition of unity 1.3e-15 (absolute).  That leaves room for
+// another libm or compiler and still catches any wrong node or weight.
+static const double QTOL = 1e-13;
+static bool rel_close(double got, double want) { return std::fabs(got - want) <= QTOL * std::fabs(want); }
+
+static void exercise_quadrature()
+{
+  using namespace hdd;
+  for (int n = 1; n <= 16; ++n) {
+    double x[16], w[16];
+    gauss_legendre01(n, x, w);
+    CHECK(x[0] > 0.0 && x[n - 1] < 1.0);
+    for (int i = 1; i < n; ++i) CHECK(x[i] > x[i - 1]);
+    for (int k = 0; k <= 2 * n - 1; ++k) {
+      double s = 0.0;
+      for (int i = 0; i < n; ++i) s += w[i] * std::pow(x[i], k);
+      CHECK(rel_close(s, 1.0 / (k + 1)));
+    }
+  }
+  const int simplex_points[14] = {1, 1, 3, 6, 6, 16, 16, 25, 25, 36, 36, 49, 49, 64};
+  double fact[16] = {1.0};
+  for (int i = 1; i < 16; ++i) fact[i] = fact[i - 1] * i;
+  for (int order = 0; order <= 13; ++order) {
+    double q[64][4];
+    const int nq = simplex_rule(order, q, 64);
+    CHECK(nq == simplex_points[order]);
+    for (int a = 0; a <= order; ++a)
+      for (int b = 0; a + b <= order; ++b) {
+        double s = 0.0;
+        for (int k = 0; k < nq; ++k) s += q[k][3] * std::pow(q[k][0], a) * std::pow(q[k][1], b);
+        CHECK(rel_close(s, fact[a] * fact[b] / fact[a + b + 2]));
+      }
+  }
+  {
+    double q[64][4];
+    CHECK(simplex_rule(13, q, 63) == -1);
+    CHECK(tensor_rule(3, 8, q, 64) == -1);   // 125 points
+  }
+  for (int dim = 1; dim <= 3; ++dim)
+    for (int order = 0; order <= 7; ++order) {
+      double q[64][4];
+      const int nq = tensor_rule(dim, order, q, 64);
+      CHECK(nq > 0);
+      for (int a = 0; a <= order; ++a) {
+        double s = 0.0;
+        for (int k = 0; k < nq; ++k) {
+          double t = q[k][3];
+          for (int d = 0; d < dim; ++d) t *= std::pow(q[k][d], a);
+          s += t;
+        }
+        CHECK(rel_close(s, std::pow(a + 1.0, -dim)));
+      }
+      if (dim <= 2) {   // the face rule: the same points, the weight in column 2
+        double f[64][3];
+        CHECK(face_rule(dim, order, f, 64) == nq);
+        for (int k = 0; k < nq; ++k) CHECK(f[k][0] == q[k][0] && f[k][1] == q[k][1] && f[k][2] == q[k][3]);
+      }
+    }
+  {
+    double f[16][3], q[16][4];
+    CHECK(face_rule(2, 8, f, 16) == -1 && tensor_rule(2, 8, q, 16) == -1);   // 25 points
+  }
+  for (int p = 1; p <= 3; ++p) {
+    for (int j = 0; j <= 10; ++j) {
+      double sv = 0.0, sd = 0.0;
+      for (int k = 0; k <= p; ++k) {
+        double v, d;
+        lagrange_1d(p, k, j / 10.0, &v, &d);
+        sv += v;
+        sd += d;
+      }
+      CHECK(std::fabs(sv - 1.0) <= QTOL && std::fabs(sd) <= QTOL);
+    }
+    for (int k = 0; k <= p; ++k)
+      for (int m = 0; m <= p; ++m) {
+        double v, d;
+        lagrange_1d(p, k, double(m) / p, &v, &d);
+        CHECK(std::fabs(v - (k == m ? 1.0 : 0.0)) <= QTOL);
+      }
+  }
+  // the hexahedral table set is these rules and polynomials laid out
+  for (int p = 1; p <= 3; ++p) {
+    double sv[8], wv[8], sf[8], wf[8], Lv[4][8], Dv[4][8], Lf[4][8], Df[4][8], Le[4][2], De[4][2];
+    hex_tables(p, p, p + 1, {sv, wv, sf, wf, Lv, Dv, Lf, Df, Le, De});
+    double x[8], w[8], v, d;
+    gauss_legendre01(p + 1, x, w);
+    for (int q = 0; q <= p; ++q) {
+      CHECK(std::fabs(sf[q] - x[q]) <= QTOL && std::fabs(wf[q] - w[q]) <= QTOL);
+      lagrange_1d(p, p, x[q], &v, &d);
+      CHECK(std::fabs(Lf[p][q] - v) <= QTOL && rel_close(Df[p][q], d));
+    }
+    for (int k = 0; k <= p; ++k)
+      CHECK(std::fabs(Le[k][0] - (k == 0 ? 1.0 : 0.0)) <= QTOL && std::fabs(Le[k][1] - (k == p ? 1.0 : 0.0)) <= QTOL);
+  }
+}
+
 int main()
 {
+  exercise_quadrature();
   // 2d structured: element types, ragged sizes, partitions, boundary kinds
   const int sizes[][4] = {{1, 1, 1, 1}, {9, 1, 1, 1}, {1, 9, 1, 1}, {16, 16, 1, 1}, {33, 17, 2, 2},
                           {65, 2, 4, 1},  {12, 8, 3, 1}, {24, 16, 4, 4}, {7, 5, 7, 5}};

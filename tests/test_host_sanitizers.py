@@ -1,7 +1,8 @@
 """Host code under AddressSanitizer + UndefinedBehaviorSanitizer (CPU only; GPU sanitizers are not available on this
 pool).  Two drivers, built here from the sources with -fsanitize=address,undefined -fno-sanitize-recover=all:
 
-- tests/host_asan/asan_host.cpp: the product's host code (csrc/host/grid.cpp, errors.cpp) through the C ABI --
+- tests/host_asan/asan_host.cpp: the quadrature rules and Lagrange tables of csrc/host/quadrature.cpp against closed
+  forms, and the product's host code (csrc/host/grid.cpp, errors.cpp) through the C ABI --
   structured 2d / 3d grids, grids from connectivity (and their rejections), rank-local views, vertex-indexed
   geometry, halo plans and send lists, checkerboard / indicator lookups, both CSR pattern builders, block-operator
   maps (the blocks must partition the monolithic pattern);
@@ -40,7 +41,8 @@ def _build_and_run(compiler, srcs, flags, out):
 def test_product_host_code_under_asan_ubsan(tmp_path):
     srcs = [os.path.join(ROOT, "tests", "host_asan", "asan_host.cpp"),
             os.path.join(ROOT, "dune-hdd_amd", "csrc", "host", "grid.cpp"),
-            os.path.join(ROOT, "dune-hdd_amd", "csrc", "host", "errors.cpp")]
+            os.path.join(ROOT, "dune-hdd_amd", "csrc", "host", "errors.cpp"),
+            os.path.join(ROOT, "dune-hdd_amd", "csrc", "host", "quadrature.cpp")]
     flags = ["-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "dune-hdd_amd", "csrc", "host")]
     _build_and_run("g++", srcs, flags, str(tmp_path / "asan_host"))
 
