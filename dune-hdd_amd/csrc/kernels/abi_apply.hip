@@ -1,0 +1,198 @@
+// dune-hdd_amd/csrc/kernels/abi_apply.hip -- C ABI: operator application on the assembled value arrays
+// (hdd_operator_apply, hdd_operator_apply2; kernels in apply_kernels.hh): what pyMOR's apply / apply2 and LRBMS's
+// local / coupling operators need from the containers SWIPDG::init() fills (base.hh:45, 260-264, 327-367;
+// block-swipdg.hh:625-676), on the device, with the theta-lincomb fused and block ranges applied in place.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+
+#include "abi_common.hh"
+#include "apply_kernels.hh"
+
+using hdd::set_error;
+using hdd::abi::fail;
+namespace dev = hdd::dev;
+
+namespace {
+const char*& last_apply_kernel_slot()
+{
+  thread_local const char* name = "";
+  return name;
+}
+
+struct ApplyPlan {
+  dev::ApplyArgs a;
+  bool tile;
+  int nb, nf;        // tile path
+  bool short_rows;   // generic path: a group of 8 lanes per row instead of a wave
+};
+
+// Every check of hdd_operator_apply's operator arguments (no device call, nothing dereferenced but host structs);
+// fills the plan except x / y.
+int plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P)
+{
+  if (!ctx || !pattern || !d_vals) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_comp < 1 || n_comp > HDD_MAX_COMP) return fail(HDD_ERR_INVALID, who, "n_comp outside 1..HDD_MAX_COMP");
+  for (int q = 0; q < n_comp; ++q)
+    if (!d_vals[q]) return fail(HDD_ERR_INVALID, who, "null value array");
+  if (pattern->n_rows < 0 || pattern->n_cols < 0 || pattern->nnz < 0) return fail(HDD_ERR_INVALID, who, "negative pattern sizes");
+  hdd_block_range rg{0, pattern->n_rows, 0, pattern->n_cols};
+  if (range) rg = *range;
+  if (rg.row_begin < 0 || rg.row_begin > rg.row_end || rg.row_end > pattern->n_rows || rg.col_begin < 0 ||
+      rg.col_begin > rg.col_end || rg.col_end > pattern->n_cols)
+    return fail(HDD_ERR_INVALID, who, "range outside the matrix");
+  dev::ApplyArgs& a = P.a;
+  a = dev::ApplyArgs{};
+  a.n_comp = n_comp;
+  bool aligned16 = true;
+  for (int q = 0; q < n_comp; ++q) {
+    a.vals[q] = d_vals[q];
+    a.theta[q] = theta ? theta[q] : 1.0;
+    aligned16 &= reinterpret_cast<uintptr_t>(d_vals[q]) % 16 == 0;
+  }
+  a.nnz = pattern->nnz;
+  a.row_ptr = pattern->row_ptr;
+  a.col = pattern->col;
+  a.row_begin = rg.row_begin;
+  a.row_end = rg.row_end;
+  a.col_begin = rg.col_begin;
+  a.col_end = rg.col_end;
+  P.tile = false;
+  if (mesh) {
+    if (!hdd::abi::mesh_faces(mesh->elem_type)) return fail(HDD_ERR_INVALID, who, "unknown element type");
+    if (mesh->own_begin < 0 || mesh->own_end > mesh->n_local || mesh->own_begin > mesh->own_end)
+      return fail(HDD_ERR_INVALID, who, "0 <= own_begin <= own_end <= n_local violated");
+    if (!mesh->neighbors) return fail(HDD_ERR_INVALID, who, "mesh without neighbors");
+    const bool two_d = (mesh->elem_type == HDD_SIMPLEX || mesh->elem_type == HDD_CUBE) && mesh->degree <= 1;
+    const int nb = two_d ? hdd::abi::mesh_nb(mesh->elem_type, 1) : 0;
+    if (two_d && pattern->n_rows != int64_t(nb) * (mesh->own_end - mesh->own_begin))
+      return fail(HDD_ERR_INVALID, who, "pattern rows != nb * owned elements of the mesh");
+    // the tile kernel: local == global numbering, nb-aligned range, aligned value stream, 32-bit byte offsets into x
+    if (two_d && pattern->elem_ptr && pattern->n_cols == int64_t(nb) * mesh->n_local && aligned16 &&
+        rg.row_begin % nb == 0 && rg.row_end % nb == 0 && rg.col_begin % nb == 0 && rg.col_end % nb == 0 &&
+        rg.col_end - rg.col_begin < (int64_t(1) << 29) && mesh->n_local < (int64_t(1) << 31)) {
+      P.tile = true;
+      P.nb = nb;
+      P.nf = hdd::abi::mesh_faces(mesh->elem_type);
+      a.elem_ptr = pattern->elem_ptr;
+      a.nbrs = mesh->neighbors;
+      a.n_local = mesh->n_local;
+      a.own_begin = mesh->own_begin;
+      a.e_begin = mesh->own_begin + rg.row_begin / nb;
+      a.e_end = mesh->own_begin + rg.row_end / nb;
+      a.ce_begin = rg.col_begin / nb;
+      a.ce_end = rg.col_end / nb;
+    }
+  }
+  if (!P.tile) {
+    if (!pattern->row_ptr || !pattern->col) return fail(HDD_ERR_INVALID, who, "pattern without row_ptr / col");
+    P.short_rows = pattern->n_rows == 0 || pattern->nnz / std::max<int64_t>(pattern->n_rows, 1) <= 32;
+  }
+  return HDD_OK;
+}
+
+template <int NB, int NF>
+hipError_t launch_tile(const hdd_ctx* ctx, const dev::ApplyArgs& a, bool multi, hipStream_t s)
+{
+  using I = dev::ApplyImage<NB, NF>;
+  const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
+  // as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB); tile_range wants a multiple of 8 workgroups
+  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / I::BYTES));
+  int64_t G = std::max<int64_t>(8, (int64_t(ctx->n_cu) * per_cu) & ~int64_t(7));
+  if (G >= n_tiles) G = n_tiles;
+  static const char* names[2] = {NB == 3 ? "apply_tile_kernel<3, 3, 1>" : "apply_tile_kernel<4, 4, 1>",
+                                 NB == 3 ? "apply_tile_kernel<3, 3, 4>" : "apply_tile_kernel<4, 4, 4>"};
+  last_apply_kernel_slot() = names[multi];
+  if (multi)
+    hipLaunchKernelGGL((dev::apply_tile_kernel<NB, NF, dev::APPLY_NV>), dim3(unsigned(G)), dim3(64), I::BYTES, s, a, n_tiles);
+  else
+    hipLaunchKernelGGL((dev::apply_tile_kernel<NB, NF, 1>), dim3(unsigned(G)), dim3(64), I::BYTES, s, a, n_tiles);
+  return hipGetLastError();
+}
+
+template <int G>
+hipError_t launch_csr(const dev::ApplyArgs& a, bool multi, hipStream_t s)
+{
+  const int64_t n_rows = a.row_end - a.row_begin;
+  const int64_t per_wg = 256 / G;
+  const unsigned grid = unsigned(std::min<int64_t>((n_rows + per_wg - 1) / per_wg, 256 * 64));
+  static const char* names[2] = {G == 8 ? "apply_csr_kernel<8, 1>" : "apply_csr_kernel<64, 1>",
+                                 G == 8 ? "apply_csr_kernel<8, 4>" : "apply_csr_kernel<64, 4>"};
+  last_apply_kernel_slot() = names[multi];
+  if (multi) hipLaunchKernelGGL((dev::apply_csr_kernel<G, dev::APPLY_NV>), dim3(grid), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((dev::apply_csr_kernel<G, 1>), dim3(grid), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+// the launches of a checked plan: the values are read once per group of APPLY_NV vectors
+int run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
+              int32_t n_vec, void* stream)
+{
+  if (P.a.row_end == P.a.row_begin) return HDD_OK;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int v0 = 0; v0 < n_vec; v0 += dev::APPLY_NV) {
+    dev::ApplyArgs a = P.a;
+    a.nv = std::min<int>(dev::APPLY_NV, n_vec - v0);
+    a.x = d_x + int64_t(v0) * ldx;
+    a.ldx = ldx;
+    a.y = d_y + int64_t(v0) * ldy;
+    a.ldy = ldy;
+    const bool multi = a.nv > 1;
+    if (P.tile) e = P.nb == 3 ? launch_tile<3, 3>(ctx, a, multi, s) : launch_tile<4, 4>(ctx, a, multi, s);
+    else e = P.short_rows ? launch_csr<8>(a, multi, s) : launch_csr<64>(a, multi, s);
+    if (e != hipSuccess) return hip_fail(e, who);
+  }
+  return HDD_OK;
+}
+}  // namespace
+
+extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot(); }
+
+extern "C" int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,
+                                  const double* const* d_vals, int32_t n_comp, const double* theta,
+                                  const hdd_block_range* range, const double* d_x, int64_t ldx, double* d_y,
+                                  int64_t ldy, int32_t n_vec, void* stream)
+{
+  const char* who = "hdd_operator_apply";
+  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_vec < 1 || n_vec > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_vec outside 1..HDD_MAX_VEC");
+  ApplyPlan P;
+  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, P)) return rc;
+  if (ldx < P.a.col_end - P.a.col_begin || ldy < P.a.row_end - P.a.row_begin)
+    return fail(HDD_ERR_INVALID, who, "ldx / ldy smaller than the range");
+  return run_apply(who, ctx, P, d_x, ldx, d_y, ldy, n_vec, stream);
+}
+
+extern "C" int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,
+                                   const double* const* d_vals, int32_t n_comp, const double* theta,
+                                   const hdd_block_range* range, const double* d_v, int64_t ldv, int32_t n_v,
+                                   const double* d_u, int64_t ldu, int32_t n_u, double* d_work, int64_t ldw,
+                                   double* d_out, void* stream)
+{
+  const char* who = "hdd_operator_apply2";
+  if (!d_v || !d_u || !d_work || !d_out) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_v < 1 || n_v > HDD_MAX_VEC || n_u < 1 || n_u > HDD_MAX_VEC)
+    return fail(HDD_ERR_INVALID, who, "n_v / n_u outside 1..HDD_MAX_VEC");
+  ApplyPlan P;
+  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, P)) return rc;
+  const int64_t rows = P.a.row_end - P.a.row_begin;
+  if (ldu < P.a.col_end - P.a.col_begin || ldv < rows || ldw < rows)
+    return fail(HDD_ERR_INVALID, who, "ldv / ldu / ldw smaller than the range");
+  if (!ctx->apply2_ws) return fail(HDD_ERR_INVALID, who, "context without its reduction buffer");
+  if (int rc = run_apply(who, ctx, P, d_u, ldu, d_work, ldw, n_u, stream)) return rc;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int blocks = int(std::min<int64_t>(dev::APPLY2_BLOCKS, std::max<int64_t>(1, (rows + 1023) / 1024)));
+  hipLaunchKernelGGL(dev::apply2_partial_kernel, dim3(blocks), dim3(256), 0, s, d_v, ldv, n_v, d_work, ldw, n_u, rows,
+                     ctx->apply2_ws);
+  e = hipGetLastError();
+  if (e != hipSuccess) return hip_fail(e, who);
+  hipLaunchKernelGGL(dev::apply2_final_kernel, dim3(1), dim3(64), 0, s, ctx->apply2_ws, blocks, n_v, n_u, d_out);
+  e = hipGetLastError();
+  return e == hipSuccess ? HDD_OK : hip_fail(e, who);
+}

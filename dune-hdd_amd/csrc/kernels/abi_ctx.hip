@@ -32,6 +32,13 @@ extern "C" int hdd_ctx_create(int hip_device, hdd_ctx** out)
   if (const char* w = getenv("HDD_P1_WGCU")) c->wgcu = std::max(0, atoi(w));
   if (const char* r = getenv("HDD_Q3G_REPS")) c->q3g_reps = std::max(0, atoi(r));
 #endif
+  // hdd_operator_apply2 reduces through this buffer and may not allocate: 512 blocks x 64 (i, j) pairs
+  e = hipMalloc(reinterpret_cast<void**>(&c->apply2_ws), size_t(512) * HDD_MAX_VEC * HDD_MAX_VEC * sizeof(double));
+  if (e != hipSuccess) {
+    c->apply2_ws = nullptr;
+    delete c;
+    return hip_fail(e, "hdd_ctx_create: hipMalloc");
+  }
   *out = c;
   return HDD_OK;
 }

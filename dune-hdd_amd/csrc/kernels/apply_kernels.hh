@@ -1,0 +1,279 @@
+// dune-hdd_amd/csrc/kernels/apply_kernels.hh -- operator application y = (sum_q theta_q A_q) x on the assembled
+// value arrays (hdd_operator_apply / hdd_operator_apply2, abi_apply.hip).
+//
+// apply_tile_kernel -- the assembler run backwards, for 2d P1 / Q1 SWIPDG patterns in local == global numbering.  One
+//   wave owns a tile of 64 consecutive elements of the row range (persistent over tiles, the assembler's tile_range
+//   XCD sweep).  The tile's row blocks are ONE contiguous CSR value range [elem_ptr[t0], elem_ptr[t0 + 64)): the wave
+//   streams it with aligned 16-byte buffer loads (origin base_al = base & ~1, as the assembler's image), combines the
+//   components with theta on the way (one image whatever n_comp) and writes it into an LDS image (XOR-swizzled
+//   against the bank conflicts of row blocks 36 / 80 values apart, apply_swz).  Lane l then takes
+//   element t0 + l: its row block starts at the ballot prefix sum of the block counts (tile_offset), its block
+//   columns are its own id and its face neighbours' ids sorted ascending -- the ordering hdd_dg_pattern_fill gave the
+//   blocks -- so neither col nor row_ptr is read: 8 B per nonzero instead of 12.  Blocks whose element lies outside
+//   the column range are skipped (their values are never multiplied).  Every indexed read of x and the value stream
+//   go through buffer resources with the true sizes: an index the mesh got wrong reads zero instead of faulting.
+//   No pipelining across tiles inside a wave: several waves per CU (8 P1 images, 4 Q1 images fit the LDS) overlap
+//   one wave's loads with another's arithmetic, and a wave has up to 20 KB of loads in flight by itself.
+// apply_csr_kernel -- plain CSR on row_ptr / col for everything else; a group of G lanes per row (8 for the short
+//   rows of P1 / Q1 / volume patterns, a wave for the hexahedral Q_p rows), shuffle reduction in a fixed order.
+// apply2_partial_kernel / apply2_final_kernel -- out[i][j] = v_i . w_j in two deterministic stages.
+// No atomics anywhere: results are bit-identical from call to call.
+#pragma once
+#include <cstdint>
+
+#include "swipdg_persistent.hh"
+
+namespace hdd {
+namespace dev {
+
+constexpr int APPLY_NV = 4;          // vectors per pass of the compile-time multi-vector kernels
+constexpr int APPLY2_BLOCKS = 512;   // partial sums per (i, j) pair of apply2 (the context's scratch holds them)
+constexpr int APPLY2_PAIRS = HDD_MAX_VEC * HDD_MAX_VEC;
+
+struct ApplyArgs {
+  const double* vals[HDD_MAX_COMP];
+  double theta[HDD_MAX_COMP];
+  int32_t n_comp, nv;                  // nv: vectors of this pass (<= the kernel's NV)
+  int64_t nnz;
+  const int64_t* row_ptr;              // generic path
+  const int32_t* col;
+  const int64_t* elem_ptr;             // tile path
+  const int32_t* nbrs;
+  int64_t n_local, own_begin;
+  int64_t e_begin, e_end;              // tile path: local element ids of the row range
+  int64_t ce_begin, ce_end;            //            and of the column range
+  int64_t row_begin, row_end, col_begin, col_end;
+  const double* x;                     // x[v * ldx + col - col_begin]
+  int64_t ldx;
+  double* y;                           // y[v * ldy + row - row_begin]
+  int64_t ldy;
+};
+
+// sizes of the tile kernel's LDS image: 16-byte chunks per lane (odd row blocks, P1: the image origin may lie one
+// value in front of the tile) and how many of them are loaded back to back
+template <int NB, int NF>
+struct ApplyImage {
+  static constexpr int BB = NB * NB, RB = BB * (NF + 1);
+  static constexpr int CHUNKS = (32 * RB + (BB % 2) + 63) / 64;
+  static constexpr int U = CHUNKS % 20 == 0 ? 20 : CHUNKS;   // P1: 19 at once; Q1: 40 in two bursts of 20
+  static constexpr int BYTES = CHUNKS * 64 * 16;
+  static_assert(CHUNKS % U == 0 && U <= 20, "burst length divides the chunk count");
+};
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t apply_rsrc(const double* p, uint32_t nbytes)
+{
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(p), (short)0, int(nbytes), 0x00020000);
+}
+
+// a wave-uniform 64-bit value (value arrays pass 2^31 entries at the large configurations)
+__device__ __forceinline__ int64_t apply_uni64(int64_t v)
+{
+  const uint32_t lo = __builtin_amdgcn_readfirstlane(uint32_t(v));
+  const uint32_t hi = __builtin_amdgcn_readfirstlane(uint32_t(uint64_t(v) >> 32));
+  return int64_t((uint64_t(hi) << 32) | lo);
+}
+
+// LDS position of image value p.  The lanes read row blocks RB values apart (P1: 36, Q1: 80 -- 8 and 2 distinct
+// 8-byte banks per 32 lanes in a plain image): bits 5..8 of the position are XORed onto bits 1..4, which spreads
+// the lanes' reads over the 16 bank pairs a 16-byte-aligned pair layout can reach; a 16-byte chunk c moves as a
+// whole to c ^ ((c >> 4) & 15), so the staging writes stay aligned and conflict-free.
+__device__ __forceinline__ int apply_swz(int p) { return p ^ (((p >> 5) & 15) << 1); }
+
+template <int NB, int NF, int NV>
+__global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
+{
+  using I = ApplyImage<NB, NF>;
+  constexpr int CH = I::CHUNKS, U = I::U;
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const int lane = threadIdx.x;
+  const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
+  const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
+  __amdgpu_buffer_rsrc_t xr[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
+  for (int64_t t = r.t; t < r.t_end; t += r.t_step) {
+    const int64_t t0 = a.e_begin + t * 64;
+    const int64_t tend = t0 + 64 < a.e_end ? t0 + 64 : a.e_end;
+    const bool active = t0 + lane < tend;
+    const int64_t e = active ? t0 + lane : t0;
+    int nbr[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) nbr[f] = a.nbrs[f * a.n_local + e];
+    const int64_t base = apply_uni64(a.elem_ptr[t0 - a.own_begin]);
+    const int64_t tile_end = apply_uni64(a.elem_ptr[tend - a.own_begin]);
+    const int64_t base_al = base & ~int64_t(1);
+    const int tlen_al = int(tile_end - base_al);   // image length in values, from the aligned origin
+    // the previous tile's image has been read by every lane
+    lds_wave_sync();
+    // [stream the tile's values -> theta combination -> LDS image]; chunks beyond the tile read zero (range check)
+    const uint32_t vbytes = tile_end > base_al ? uint32_t(tlen_al) * 8u : 0u;
+#pragma unroll 1
+    for (int k0 = 0; k0 < CH; k0 += U) {
+      if (k0 * 128 >= tlen_al) break;
+      dvec2 v[U];
+      {
+        const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[0] + base_al, vbytes);
+        const double th = a.theta[0];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = th * ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
+      }
+#pragma unroll 1
+      for (int q = 1; q < a.n_comp; ++q) {
+        const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
+        const double th = a.theta[q];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const dvec2 w = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
+          v[u].x = __builtin_fma(th, w.x, v[u].x);
+          v[u].y = __builtin_fma(th, w.y, v[u].y);
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
+    }
+    // an odd image length: the last value has no whole 16-byte chunk inside the tile's range
+    if ((tlen_al & 1) && lane == 0) {
+      const uint32_t o8 = uint32_t(tlen_al - 1) * 8u;
+      double s = a.theta[0] * ld64f(apply_rsrc(a.vals[0] + base_al, vbytes), o8);
+      for (int q = 1; q < a.n_comp; ++q) s = __builtin_fma(a.theta[q], ld64f(apply_rsrc(a.vals[q] + base_al, vbytes), o8), s);
+      lds[apply_swz(tlen_al - 1)] = s;
+    }
+    lds_wave_sync();
+    // [lane = element: row block from the image, block columns from the neighbours, x gathered per block]
+    int nint = 0;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) nint += nbr[f] >= 0;
+    const int off = tile_offset<NB>(nint, active) + int(base - base_al);
+    if (!active) continue;
+    int id[NF + 1];
+    id[0] = int(e);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) id[f + 1] = nbr[f] >= 0 ? nbr[f] : 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+      for (int j = 0; j < NF - i; ++j) {
+        const int lo = id[j] < id[j + 1] ? id[j] : id[j + 1], hi = id[j] < id[j + 1] ? id[j + 1] : id[j];
+        id[j] = lo;
+        id[j + 1] = hi;
+      }
+    const int rl = NB * (nint + 1);   // row length
+    double acc[NV][NB];
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) acc[v][i] = 0.0;
+#pragma unroll
+    for (int b = 0; b <= NF; ++b) {
+      if (b > nint || id[b] < a.ce_begin || id[b] >= a.ce_end) continue;   // skipped, not multiplied by zero
+      const uint32_t xo = uint32_t(id[b] - int(a.ce_begin)) * uint32_t(NB * 8);
+      double xv[NV][NB];
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) xv[v][j] = v < a.nv ? ld64f(xr[v], xo + 8u * j) : 0.0;
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const double m = lds[apply_swz(off + i * rl + b * NB + j)];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) acc[v][i] = __builtin_fma(m, xv[v][j], acc[v][i]);
+        }
+    }
+    double* yo = a.y + (e - a.e_begin) * NB;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if (v < a.nv)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) yo[v * a.ldy + i] = acc[v][i];
+  }
+}
+
+// G lanes per row, 256 / G rows per workgroup pass
+template <int G, int NV>
+__global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
+{
+  const int gl = threadIdx.x % G;
+  const int64_t n_rows = a.row_end - a.row_begin;
+  const int64_t stride = int64_t(gridDim.x) * (256 / G);
+  for (int64_t rr = int64_t(blockIdx.x) * (256 / G) + threadIdx.x / G; rr < n_rows; rr += stride) {
+    int64_t k0 = a.row_ptr[a.row_begin + rr], k1 = a.row_ptr[a.row_begin + rr + 1];
+    k0 = k0 < 0 ? 0 : k0;
+    k1 = k1 > a.nnz ? a.nnz : k1;
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    for (int64_t k = k0 + gl; k < k1; k += G) {
+      const int64_t c = a.col[k];
+      if (c < a.col_begin || c >= a.col_end) continue;   // skipped, not multiplied by zero
+      double m = a.theta[0] * a.vals[0][k];
+      for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
+      const double* xc = a.x + (c - a.col_begin);
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) acc[v] = __builtin_fma(m, xc[v * a.ldx], acc[v]);
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int s = G / 2; s > 0; s >>= 1) acc[v] += __shfl_xor(acc[v], s, G);
+    if (gl == 0)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
+  }
+}
+
+// apply2, stage 1: partial[block][i * HDD_MAX_VEC + j] = sum over the block's rows of v_i[r] w_j[r] (fixed row ->
+// thread assignment, shuffle tree, then the four waves in order)
+__global__ void __launch_bounds__(256) apply2_partial_kernel(const double* v, int64_t ldv, int n_v, const double* w,
+                                                             int64_t ldw, int n_u, int64_t n, double* partial)
+{
+  __shared__ double red[4][APPLY2_PAIRS];
+  double acc[HDD_MAX_VEC][HDD_MAX_VEC];
+#pragma unroll
+  for (int i = 0; i < HDD_MAX_VEC; ++i)
+#pragma unroll
+    for (int j = 0; j < HDD_MAX_VEC; ++j) acc[i][j] = 0.0;
+  for (int64_t r = int64_t(blockIdx.x) * 256 + threadIdx.x; r < n; r += int64_t(gridDim.x) * 256) {
+    double vi[HDD_MAX_VEC], wj[HDD_MAX_VEC];
+#pragma unroll
+    for (int i = 0; i < HDD_MAX_VEC; ++i) vi[i] = i < n_v ? v[i * ldv + r] : 0.0;
+#pragma unroll
+    for (int j = 0; j < HDD_MAX_VEC; ++j) wj[j] = j < n_u ? w[j * ldw + r] : 0.0;
+#pragma unroll
+    for (int i = 0; i < HDD_MAX_VEC; ++i)
+#pragma unroll
+      for (int j = 0; j < HDD_MAX_VEC; ++j) acc[i][j] = __builtin_fma(vi[i], wj[j], acc[i][j]);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < HDD_MAX_VEC; ++i)
+#pragma unroll
+    for (int j = 0; j < HDD_MAX_VEC; ++j) {
+      double s = acc[i][j];
+      if (i < n_v && j < n_u)   // (uniform)
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+      if (lane == 0) red[wave][i * HDD_MAX_VEC + j] = s;
+    }
+  __syncthreads();
+  if (threadIdx.x < APPLY2_PAIRS) {
+    const int p = threadIdx.x;
+    partial[int64_t(blockIdx.x) * APPLY2_PAIRS + p] = ((red[0][p] + red[1][p]) + red[2][p]) + red[3][p];
+  }
+}
+
+// stage 2: out[i * n_u + j] = the blocks' partial sums, in block order
+__global__ void __launch_bounds__(64) apply2_final_kernel(const double* partial, int n_blocks, int n_v, int n_u, double* out)
+{
+  const int p = threadIdx.x, i = p / HDD_MAX_VEC, j = p % HDD_MAX_VEC;
+  if (i >= n_v || j >= n_u) return;
+  double s = 0.0;
+  for (int b = 0; b < n_blocks; ++b) s += partial[int64_t(b) * APPLY2_PAIRS + p];
+  out[i * n_u + j] = s;
+}
+
+}  // namespace dev
+}  // namespace hdd

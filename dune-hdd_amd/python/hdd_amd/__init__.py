@@ -98,6 +98,13 @@ class CsrT(C.Structure):
                 ("col", C.c_void_p), ("elem_ptr", C.c_void_p)]
 
 
+class BlockRange(C.Structure):
+    _fields_ = [("row_begin", C.c_int64), ("row_end", C.c_int64), ("col_begin", C.c_int64), ("col_end", C.c_int64)]
+
+
+MAX_VEC = 8
+
+
 class ShardInfo(C.Structure):
     _fields_ = [("n_local", C.c_int64), ("own_begin", C.c_int64), ("own_end", C.c_int64), ("n_ghost", C.c_int64),
                 ("global_first", C.c_int64), ("n_rows", C.c_int64), ("n_cols", C.c_int64), ("nnz", C.c_int64),
@@ -214,6 +221,10 @@ def lib():
         "hdd_block_step_sync": (_I32, [_VP, _VP, C.c_double]),
         "hdd_device_hub_stall": (_I32, [_VP, _I32, C.c_double]),
         "hdd_device_hub_release": (_I32, [_VP]),
+        "hdd_operator_apply": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP]),
+        "hdd_operator_apply2": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _I32, _VP, _I64, _I32, _VP, _I64,
+                                       _VP, _VP]),
+        "hdd_last_apply_kernel": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -221,6 +232,12 @@ def lib():
         fn.argtypes = args
     _LIB = L
     return L
+
+
+def last_apply_kernel():
+    """hdd_last_apply_kernel: the kernel this thread's last apply / apply2 launched ("apply_tile_kernel<...>" or
+    "apply_csr_kernel<...>")"""
+    return lib().hdd_last_apply_kernel().decode()
 
 
 def last_tile_kernel():
@@ -568,6 +585,8 @@ class DevicePattern:
     def __init__(self, local, device=0, host=None, ctx=None, dmesh=None, on_device=False, volume=False):
         torch = _torch()
         dev = torch.device("cuda", device)
+        self.local = local
+        self.volume = volume and not on_device   # element-local product pattern: not the mesh's face pattern
         if on_device:
             ctx = ctx or Context(device)
             dmesh = dmesh or DeviceMesh(local, device)
@@ -800,6 +819,102 @@ def affine_lincomb(ctx, comps, theta, out=None, stream=None):
     _check(lib().hdd_affine_lincomb(ctx.h, nnz, ptrs, nc, _p(theta), ns, out.data_ptr(), out.stride(0),
                                     C.c_void_p(s)), "hdd_affine_lincomb")
     return out if ret is None else ret
+
+
+class CsrPattern:
+    """A device CSR pattern from its arrays, e.g. an extracted block operator's (block_operator's row_ptr, col):
+    what apply / apply2 take in place of a DevicePattern.  No elem_ptr: such operators take the generic kernel."""
+
+    def __init__(self, row_ptr, col, n_cols):
+        self.row_ptr, self.col, self.elem_ptr, self.local = row_ptr, col, None, None
+        self.nnz = int(col.numel())
+        self.t = CsrT(int(row_ptr.numel()) - 1, int(n_cols), self.nnz, row_ptr.data_ptr(), col.data_ptr(), None)
+
+
+def _block_range(dpattern, dmesh, block, grid):
+    """block: None (the whole matrix), (ss, nn) -- the operator of subdomains ss / nn of `grid` (default: the grid of
+    the pattern's or the mesh's LocalMesh) -- or (row_begin, row_end, col_begin, col_end) / a BlockRange."""
+    if block is None or isinstance(block, BlockRange):
+        return block
+    if len(block) == 4:
+        return BlockRange(*[int(b) for b in block])
+    ss, nn = block
+    if grid is None:
+        local = getattr(dpattern, "local", None) or (dmesh.local if dmesh is not None else None)
+        if local is None:
+            raise HddError("apply: block=(ss, nn) needs a Grid (grid=, or a DevicePattern / DeviceMesh that has one)")
+        grid = local.grid
+    a, b = grid.subdomain_range(ss, ss + 1)
+    c, d = grid.subdomain_range(nn, nn + 1)
+    return BlockRange(a * grid.nb, b * grid.nb, c * grid.nb, d * grid.nb)
+
+
+def _apply_operands(dpattern, vals, theta, dmesh, block, grid):
+    vals = list(vals)
+    n = len(vals)
+    if n < 1 or n > MAX_COMP:
+        raise HddError("apply: 1..%d value arrays" % MAX_COMP)
+    ptrs = (C.c_void_p * n)(*[v.data_ptr() for v in vals])
+    th = None
+    if theta is not None:
+        th = np.ascontiguousarray(theta, np.float64).reshape(-1)
+        if th.shape[0] != n:
+            raise HddError("apply: theta needs one entry per value array")
+    rng = _block_range(dpattern, dmesh, block, grid)
+    if getattr(dpattern, "volume", False):
+        dmesh = None   # the mesh argument asserts the FACE pattern; a volume pattern takes the CSR kernel
+    rows = dpattern.t.n_rows if rng is None else rng.row_end - rng.row_begin
+    cols = dpattern.t.n_cols if rng is None else rng.col_end - rng.col_begin
+    return vals, n, ptrs, th, rng, rows, cols, dmesh
+
+
+def apply(ctx, dpattern, vals, x, theta=None, dmesh=None, block=None, out=None, stream=None, grid=None):
+    """hdd_operator_apply: y = (sum_q theta[q] A_q) x on the device, A_q = vals[q] on dpattern (theta None: all
+    ones) -- pyMOR's apply on the affinely decomposed operator at a parameter without writing A(mu).  x: [n] or
+    [n_vec, n] device float64 (rows may be strided), n_vec <= MAX_VEC; returns y in x's shape.  dmesh: the DeviceMesh
+    whose SWIPDG face pattern dpattern is -> the tile kernel (P1 / Q1, whole-grid view); None -> the CSR kernel.
+    block=(ss, nn): the BlockSWIPDG local / coupling operator (rows of ss, columns of nn; x in nn's numbering),
+    applied on the global arrays without extraction."""
+    torch = _torch()
+    vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
+    x2 = x if x.dim() == 2 else x.reshape(1, -1)
+    if x2.dtype != torch.float64 or x2.stride(1) != 1 or x2.shape[1] != cols:
+        raise HddError("apply: x must be float64 [n_vec, %d] with unit inner stride" % cols)
+    n_vec = x2.shape[0]
+    ldx = x2.stride(0) if n_vec > 1 else max(cols, 1)
+    if out is None:
+        out = torch.empty((n_vec, rows), dtype=torch.float64, device=x.device)
+    y2 = out if out.dim() == 2 else out.reshape(1, -1)
+    if y2.dtype != torch.float64 or y2.stride(1) != 1 or y2.shape != (n_vec, rows):
+        raise HddError("apply: out must be float64 [n_vec, %d] with unit inner stride" % rows)
+    ldy = y2.stride(0) if n_vec > 1 else max(rows, 1)
+    s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    _check(lib().hdd_operator_apply(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
+                                    n, _p(th), None if rng is None else C.addressof(rng), x2.data_ptr(), ldx,
+                                    y2.data_ptr(), ldy, n_vec, C.c_void_p(s)), "hdd_operator_apply")
+    return out if (x.dim() == 2 or out.dim() == 1) else out.reshape(-1)
+
+
+def apply2(ctx, dpattern, vals, v, u, theta=None, dmesh=None, block=None, stream=None, grid=None):
+    """hdd_operator_apply2: the [n_v, n_u] tensor v_i^T (sum_q theta[q] A_q) u_j (pyMOR's apply2; V^T A_q V of a
+    reduced-basis projection; a product's Gramian).  v: [n_v, rows] (or [rows]), u: [n_u, cols] (or [cols])."""
+    torch = _torch()
+    vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
+    v2 = v if v.dim() == 2 else v.reshape(1, -1)
+    u2 = u if u.dim() == 2 else u.reshape(1, -1)
+    for t, m, what in ((v2, rows, "v"), (u2, cols, "u")):
+        if t.dtype != torch.float64 or t.stride(1) != 1 or t.shape[1] != m:
+            raise HddError("apply2: %s must be float64 [k, %d] with unit inner stride" % (what, m))
+    n_v, n_u = v2.shape[0], u2.shape[0]
+    work = torch.empty((n_u, max(rows, 1)), dtype=torch.float64, device=u.device)
+    out = torch.empty((n_v, n_u), dtype=torch.float64, device=u.device)
+    s = stream if stream is not None else torch.cuda.current_stream(u.device).cuda_stream
+    _check(lib().hdd_operator_apply2(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
+                                     n, _p(th), None if rng is None else C.addressof(rng), v2.data_ptr(),
+                                     v2.stride(0) if n_v > 1 else max(rows, 1), n_v, u2.data_ptr(),
+                                     u2.stride(0) if n_u > 1 else max(cols, 1), n_u, work.data_ptr(), work.stride(0),
+                                     out.data_ptr(), C.c_void_p(s)), "hdd_operator_apply2")
+    return out
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

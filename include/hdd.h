@@ -435,6 +435,54 @@ int hdd_block_operators_values_device(hdd_ctx* ctx, const hdd_csr* pattern, int3
                                       int32_t n_comp, double* const* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* operator application -- what the reference's consumers do with the assembled containers: pyMOR's  */
+/* apply / apply2 on the LinearAffinelyDecomposedContainerBased operator of get_operator() and on the */
+/* products (base.hh:45, 260-264), LRBMS on every get_local_operator(ss) / get_coupling_operator(ss,  */
+/* nn) (block-swipdg.hh:625-676), the applies inside uncached_solve's solver (base.hh:327-367).       */
+/* Additive to ABI 8.                                                                               */
+/* ---------------------------------------------------------------------------------------------- */
+#define HDD_MAX_VEC 8
+/* y[v][r - row_begin] = sum_q theta[q] * sum_{k in row r, col_begin <= col[k] < col_end}
+ *                       d_vals[q][k] * x[v][col[k] - col_begin]
+ * for r in [row_begin, row_end), v < n_vec.  y is overwritten and must not overlap x.  x is [n_vec][ldx]
+ * (ldx >= col_end - col_begin), y is [n_vec][ldy] (ldy >= row_end - row_begin), both device.
+ * d_vals: host array of n_comp (1..HDD_MAX_COMP) device value arrays on `pattern`; theta: host [n_comp], NULL = all
+ * ones -- sum_q theta_q A_q is applied without ever being written (no hdd_affine_lincomb, no room for A(mu)).
+ * range: NULL = the whole matrix; else the operator (ss, nn) of a BlockSWIPDG is rows / columns of the element
+ * ranges of ss / nn times nb (hdd_grid_subdomain_range), applied in place, no extraction.  Entries outside the
+ * column range are skipped, not multiplied by zero: x is never read outside [0, col_end - col_begin) and a NaN in
+ * a skipped value does not reach y.
+ * mesh: NULL, or the mesh whose SWIPDG face pattern `pattern` is (hdd_pattern_fill / hdd_dg_pattern_fill with the
+ * mesh's faces / hdd_pattern_fill_device on this mesh) -- BY PASSING mesh THE CALLER ASSERTS THIS; the library
+ * cannot check it.  With a 2d HDD_SIMPLEX / HDD_CUBE mesh (degree <= 1), pattern->elem_ptr, n_cols == nb * n_local
+ * (local == global numbering: the whole-grid view), a range whose four bounds are multiples of nb, 16-byte aligned
+ * value arrays and fewer than 2^29 columns in range, the call takes the tile kernel, which derives every column from
+ * mesh->neighbors and reads neither col nor row_ptr (8 B per nonzero).  Everything else -- mesh == NULL, hexahedra,
+ * volume-only product patterns (pass mesh = NULL for them: their pattern is not the face pattern), extracted block
+ * operators, renumbered columns, a range that is not nb-aligned -- takes the plain CSR kernel on row_ptr / col with the
+ * same semantics.  hdd_last_apply_kernel() names the path taken.
+ * Asynchronous on `stream`; allocates nothing, synchronises nothing, uses no atomics: results are bit-identical
+ * from call to call.  Every argument check precedes the first device call: HDD_ERR_INVALID for a null ctx /
+ * pattern / d_vals / d_vals[q] / d_x / d_y, n_comp outside 1..HDD_MAX_COMP, n_vec outside 1..HDD_MAX_VEC, ldx / ldy
+ * too small, a range outside the matrix, a mesh that does not match the pattern's rows. */
+int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                       int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_x,
+                       int64_t ldx, double* d_y, int64_t ldy, int32_t n_vec, void* stream);
+/* d_out[i*n_u + j] = v_i^T (sum_q theta_q A_q) u_j on the same (restricted) operator; i < n_v, j < n_u, both in
+ * 1..HDD_MAX_VEC: pyMOR's apply2, a reduced-basis projection V^T A_q V, a product's Gramian.  d_v is [n_v][ldv]
+ * (ldv >= rows), d_u [n_u][ldu] (ldu >= columns), d_work the caller's [n_u][ldw] scratch, ldw >= rows; d_out device
+ * [n_v*n_u].  It is hdd_operator_apply into d_work followed by a two-stage reduction in a fixed order (per-block
+ * partial sums in a buffer the context owns since its creation, then the blocks in order): same rules as above, and
+ * one stream at a time per context. */
+int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                        int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_v,
+                        int64_t ldv, int32_t n_v, const double* d_u, int64_t ldu, int32_t n_u, double* d_work,
+                        int64_t ldw, double* d_out, void* stream);
+/* the kernel the last hdd_operator_apply / _apply2 of this thread launched ("" if none), like hdd_last_tile_kernel:
+ * "apply_tile_kernel<NB, NF, NV>" or "apply_csr_kernel<G, NV>" */
+const char* hdd_last_apply_kernel(void);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */
 /* GPU owns a contiguous range of subdomains and assembles their rows -- A_ss and A_ss,nn are written  */
 /* by the owner of ss (block-swipdg.hh:355-382, coupling 1270-1326, boundary 1136-1179), so there is  */

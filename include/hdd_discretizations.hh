@@ -647,7 +647,73 @@ class AffinelyDecomposedMatrix {
     return h;
   }
 
+  // What pyMOR does with the operator (apply / apply2 on the LinearAffinelyDecomposedContainerBased operator,
+  // base.hh:45, 260-264) -- on the device and without freeze_parameter's A(mu): y = (A_aff + sum_q theta_q(mu) A_q) x
+  // (hdd_operator_apply; theta as in freeze_parameter).  d_x [n_vec][ld], d_y [n_vec][ld] device arrays (ld >= rows
+  // and columns of the -- restricted -- operator), asynchronous on `stream`.  range: a block of the operator
+  // (BlockSWIPDG::apply_local_operator / apply_coupling_operator).  System matrices carry their mesh's face
+  // neighbours (tile_mesh) and take the tile kernel; extracted operators and products take the CSR kernel.
+  void apply(const double* d_x, double* d_y, int32_t n_vec, int64_t ld, double mu = 0.0, void* stream = nullptr,
+             const hdd_block_range* range = nullptr) const
+  {
+    std::vector<const double*> v;
+    std::vector<double> theta;
+    operands(mu, v, theta);
+    const hdd_csr pat = pattern->csr();
+    internal::check(hdd_operator_apply(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
+                                       theta.data(), range, d_x, ld, d_y, ld, n_vec, stream), "hdd_operator_apply");
+  }
+  std::vector<double> apply(const std::vector<double>& x, double mu = 0.0, const hdd_block_range* range = nullptr) const
+  {
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    const int64_t cols = range ? range->col_end - range->col_begin : pattern->cols;
+    if (int64_t(x.size()) != cols) throw Stuff::Exceptions::wrong_input_given("apply: x has the wrong size");
+    const int64_t ld = std::max<int64_t>(std::max(rows, cols), 1);
+    internal::DeviceArray<double> dx{size_t(ld)}, dy{size_t(ld)};
+    if (cols) internal::hip_check(hipMemcpy(dx.get(), x.data(), size_t(cols) * sizeof(double), hipMemcpyHostToDevice), "apply");
+    apply(dx.get(), dy.get(), 1, ld, mu, nullptr, range);
+    internal::hip_check(hipDeviceSynchronize(), "apply");
+    auto y = dy.download();
+    y.resize(size_t(rows));
+    return y;
+  }
+  // v^T A(mu) u (hdd_operator_apply2)
+  double apply2(const std::vector<double>& v, const std::vector<double>& u, double mu = 0.0) const
+  {
+    if (int64_t(v.size()) != pattern->rows || int64_t(u.size()) != pattern->cols)
+      throw Stuff::Exceptions::wrong_input_given("apply2: v / u have the wrong size");
+    std::vector<const double*> a;
+    std::vector<double> theta;
+    operands(mu, a, theta);
+    internal::DeviceArray<double> dv(v), du(u), work{size_t(std::max<int64_t>(pattern->rows, 1))}, out{size_t(1)};
+    const hdd_csr pat = pattern->csr();
+    internal::check(hdd_operator_apply2(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, a.data(), int32_t(a.size()),
+                                        theta.data(), nullptr, dv.get(), std::max<int64_t>(pattern->rows, 1), 1,
+                                        du.get(), std::max<int64_t>(pattern->cols, 1), 1, work.get(),
+                                        std::max<int64_t>(pattern->rows, 1), out.get(), nullptr), "hdd_operator_apply2");
+    internal::hip_check(hipDeviceSynchronize(), "apply2");
+    return out.download()[0];
+  }
+  // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
+  // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
+  void set_tile_mesh(const hdd_mesh& m, std::shared_ptr<internal::DeviceArray<int32_t>> nbrs)
+  {
+    tile_nbrs = std::move(nbrs);
+    tile_mesh = hdd_mesh{m.elem_type, m.degree, m.n_local, m.own_begin, m.own_end, nullptr, tile_nbrs->get(), nullptr,
+                         nullptr, nullptr};
+  }
+  std::shared_ptr<internal::DeviceArray<int32_t>> tile_nbrs;   // null: the CSR kernel
+  hdd_mesh tile_mesh{};
+
  private:
+  // the value arrays and theta(mu) of A(mu), the affine part at 1 (as freeze_parameter)
+  void operands(double mu, std::vector<const double*>& v, std::vector<double>& theta) const
+  {
+    if (affine) { v.push_back(affine->get()); theta.push_back(1.0); }
+    for (size_t q = 0; q < comps.size(); ++q) { v.push_back(comps[q]->get()); theta.push_back(coefficients[q].evaluate(mu)); }
+    if (v.empty() || v.size() > HDD_MAX_COMP)
+      throw Stuff::Exceptions::wrong_input_given("apply: 1..HDD_MAX_COMP value arrays expected");
+  }
   std::vector<double> trimmed(const internal::DeviceArray<double>& a) const
   {
     auto h = a.download();
@@ -898,6 +964,11 @@ class SWIPDG {
     matrix_ = AffinelyDecomposedMatrix();
     matrix_.pattern = pattern_;
     matrix_.ctx = ctx_;
+    // apply / apply2 on the system matrix take the tile kernel when the columns are the local element numbering
+    // (the whole-grid view); the local layer and subset grids with other column ids take the CSR kernel
+    bool identity = layer_ == Layer::leaf && info_.dim == 2;
+    for (size_t e = 0; identity && e < gid_.size(); ++e) identity = gid_[e] == int64_t(e);
+    if (identity) matrix_.set_tile_mesh(mesh_, internal::device_copy(d_nbrs_));
     const auto& K = problem_.diffusion_factor;
     matrix_.coefficients = K.coefficients;
     for (const auto& c : K.components) matrix_.comps.push_back(assemble_lhs(c, pat));
@@ -1389,6 +1460,24 @@ class BlockSWIPDG : public SWIPDG {
     return extract(ss, nn);
   }
 
+  // get_local_operator(ss) / get_coupling_operator(ss, nn) applied to a vector WITHOUT extracting them: rows of ss
+  // and columns of nn of the global matrix through a block range (hdd_operator_apply), A(mu) fused.  x in nn's local
+  // numbering, the result in ss's.  A non-neighbour is rejected as by get_coupling_operator.
+  std::vector<double> apply_local_operator(int ss, const std::vector<double>& x, double mu = 0.0) const
+  {
+    range_check(ss);
+    return apply_block(ss, ss, x, mu);
+  }
+  std::vector<double> apply_coupling_operator(int ss, int nn, const std::vector<double>& x, double mu = 0.0) const
+  {
+    range_check(ss);
+    if (!neighbours_[size_t(ss)].count(nn))
+      throw Stuff::Exceptions::index_out_of_range("Subdomain " + std::to_string(nn) + " is not a neighbour of subdomain " +
+                                                  std::to_string(ss) + " (call neighbouring_subdomains(" +
+                                                  std::to_string(ss) + ") to find out)!");
+    return apply_block(ss, nn, x, mu);
+  }
+
   // block-swipdg.hh:678-685: the local vector of ss (local discretization rhs + boundary contributions) =
   // the rows of ss of the global rhs, component by component
   AffinelyDecomposedVector get_local_functional(int ss) const
@@ -1587,6 +1676,16 @@ class BlockSWIPDG : public SWIPDG {
     if (ss < 0 || ss >= num_subdomains())
       throw Stuff::Exceptions::index_out_of_range("0 <= ss < num_subdomains() = " + std::to_string(num_subdomains()) +
                                                   " is not true for ss = " + std::to_string(ss) + "!");
+  }
+
+  std::vector<double> apply_block(int ss, int nn, const std::vector<double>& x, double mu) const
+  {
+    int64_t a, b, c, d;
+    internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &b), "range");
+    internal::check(hdd_grid_subdomain_range(grid_, nn, nn + 1, &c, &d), "range");
+    const int64_t nb = info_.nb;
+    const hdd_block_range rng{a * nb, b * nb, c * nb, d * nb};
+    return system_matrix().apply(x, mu, &rng);
   }
 
   // block-swipdg.hh:625-676: rows of ss, columns of nn, both in local numbering -- extracted on the device from
