@@ -326,9 +326,12 @@ def sigma_boundary(p):
     return SIGMA_BOUNDARY.get(p, 99.0)
 
 
+QP_GRID_GRADED = 0x100      # OR_QP_GRID_GRADED: or'ed into QpGridT.dim when the struct carries nodes
+
+
 class QpGridT(C.Structure):
     _fields_ = [("dim", C.c_int32), ("degree", C.c_int32), ("n", C.c_int64 * 3),
-                ("lower", C.c_double * 3), ("upper", C.c_double * 3)]
+                ("lower", C.c_double * 3), ("upper", C.c_double * 3), ("nodes", C.c_void_p * 3)]
 
 
 class QpTensorT(C.Structure):
@@ -355,14 +358,24 @@ def _qp_lib():
 
 class QpGrid:
     """Structured grid of n[0] x n[1] (x n[2]) axis-aligned cubes on [lower, upper] carrying DG Q_p;
-    element id = i + n0 (j + n1 k) (lexicographic, x fastest)."""
+    element id = i + n0 (j + n1 k) (lexicographic, x fastest).  nodes: optional per-axis breakpoint arrays
+    (axis a: n[a] + 1 increasing values, None = equidistant on [lower[a], upper[a]]) for a graded grid."""
 
-    def __init__(self, dim, p, n, lower, upper):
+    def __init__(self, dim, p, n, lower, upper, nodes=None):
         self.dim, self.p = int(dim), int(p)
         n = list(n) + [1] * (3 - len(n))
         lo = list(lower) + [0.0] * (3 - len(lower))
         up = list(upper) + [1.0] * (3 - len(upper))
-        self.t = QpGridT(self.dim, self.p, (C.c_int64 * 3)(*n), (C.c_double * 3)(*lo), (C.c_double * 3)(*up))
+        nodes = list(nodes or []) + [None] * 3
+        self.nodes = [None if a >= self.dim or nodes[a] is None else np.array(nodes[a], np.float64)
+                      for a in range(3)]                 # owned copies: the struct only holds their addresses
+        for a, nd in enumerate(self.nodes):
+            if nd is not None and (nd.shape != (n[a] + 1,) or not np.all(np.diff(nd) > 0)):
+                raise ValueError("nodes[%d] must be %d increasing breakpoints" % (a, n[a] + 1))
+        graded = any(nd is not None for nd in self.nodes)     # the library reads `nodes` only under this flag
+        self.t = QpGridT(self.dim | (QP_GRID_GRADED if graded else 0), self.p, (C.c_int64 * 3)(*n),
+                         (C.c_double * 3)(*lo), (C.c_double * 3)(*up),
+                         (C.c_void_p * 3)(*[_ptr(nd) for nd in self.nodes]))
         self.nb = (self.p + 1) ** self.dim
         self.ne = int(_qp_lib().or_qp_num_elements(C.byref(self.t)))
         if self.ne < 0:

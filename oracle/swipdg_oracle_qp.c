@@ -15,6 +15,9 @@
  *   - penalty sigma * kappa^- kappa^+ gamma / |F|^beta with |F| the face volume (area in 3D), beta=1/(d-1).
  * The DG space is dune-gdt's DiscontinuousLagrange (swipdg.hh:94): Q_p Lagrange shape functions with
  * equidistant nodes, DoFs numbered lexicographically (x fastest) inside the element, element-blocked.
+ * The grid is equidistant on [lower, upper] or, with OR_QP_GRID_GRADED and or_qp_grid_t::nodes, rectilinear
+ * with per-axis breakpoints (graded: neighbours of different size); geometry() is the only place that knows
+ * which.  `nodes` is read only under that flag: a caller that still passes the earlier struct stays valid.
  *
  * Pinning: at d=2, p=1 this restatement must reproduce swipdg_oracle.c (pinned to the reference's ESV2007
  * expectation tables) entry for entry -- tests/test_oracle_qp.py.  For p>1 and d=3 there is no reference
@@ -88,12 +91,14 @@ typedef struct {
   int dim, p, nb, nf;
   int64_t n[3], ne;
   double lower[3], upper[3];
+  const double* nodes[3];
 } qgrid_t;
 
 static int init_grid(const or_qp_grid_t* in, qgrid_t* g)
 {
-  if (in->dim < 2 || in->dim > 3 || in->degree < 1 || in->degree > QP_MAXP) return -1;
-  g->dim = in->dim;
+  const int graded = (in->dim & OR_QP_GRID_GRADED) != 0, dim = in->dim & ~OR_QP_GRID_GRADED;
+  if (dim < 2 || dim > 3 || in->degree < 1 || in->degree > QP_MAXP) return -1;
+  g->dim = dim;
   g->p = in->degree;
   g->nb = 1;
   g->ne = 1;
@@ -101,6 +106,7 @@ static int init_grid(const or_qp_grid_t* in, qgrid_t* g)
     g->n[a] = a < g->dim ? in->n[a] : 1;
     g->lower[a] = in->lower[a];
     g->upper[a] = in->upper[a];
+    g->nodes[a] = graded && a < g->dim ? in->nodes[a] : NULL;   /* (not read from a struct without the flag) */
     if (a < g->dim) {
       if (g->n[a] < 1) return -1;
       g->nb *= g->p + 1;
@@ -143,8 +149,9 @@ static void geometry(const qgrid_t* g, int64_t e, geo_t* G)
   memset(G->J, 0, sizeof(G->J));
   memset(G->Jinv, 0, sizeof(G->Jinv));
   for (int a = 0; a < d; ++a) {
-    const double x0 = linspace_node(g->lower[a], g->upper[a], g->n[a], ijk[a]);
-    const double x1 = linspace_node(g->lower[a], g->upper[a], g->n[a], ijk[a] + 1);
+    const double* nd = g->nodes[a];   /* graded axis: the caller's breakpoints */
+    const double x0 = nd ? nd[ijk[a]] : linspace_node(g->lower[a], g->upper[a], g->n[a], ijk[a]);
+    const double x1 = nd ? nd[ijk[a] + 1] : linspace_node(g->lower[a], g->upper[a], g->n[a], ijk[a] + 1);
     G->v0[a] = x0;
     G->J[a][a] = x1 - x0;
   }

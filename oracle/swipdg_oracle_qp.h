@@ -1,6 +1,6 @@
 /*
  * oracle/swipdg_oracle_qp.h -- TEST INFRASTRUCTURE ONLY.
- * CPU restatement of the SWIPDG stiffness assembly for DG Q_p on structured 2D/3D cube grids (see the .c
+ * CPU restatement of the SWIPDG stiffness assembly for DG Q_p on structured (equidistant or graded) 2D/3D cube grids (see the .c
  * header).  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use it.
  */
 #ifndef HDD_SWIPDG_ORACLE_QP_H
@@ -14,12 +14,17 @@ extern "C" {
 enum { OR_QP_FN_CONST = 0, OR_QP_FN_PER_ELEM = 1, OR_QP_FN_SINUSOID = 2, OR_QP_FN_COS_PRODUCT = 3 };
 enum { OR_QP_TENSOR_CONST = 0, OR_QP_TENSOR_ISO_PER_ELEM = 1, OR_QP_TENSOR_SYM_PER_ELEM = 2 };
 enum { OR_QP_BOUNDARY_DIRICHLET = 0, OR_QP_BOUNDARY_NEUMANN = 1 };
+/* or'ed into or_qp_grid_t::dim: the struct carries `nodes`.  Without it `nodes` is never read, so a caller built
+ * against the earlier struct, which ended after `upper`, stays valid. */
+enum { OR_QP_GRID_GRADED = 0x100 };
 
 typedef struct {
-  int32_t dim;                /* 2 or 3 */
+  int32_t dim;                /* 2 or 3 [| OR_QP_GRID_GRADED] */
   int32_t degree;             /* p = 1..4 */
   int64_t n[3];               /* elements per direction; element id = i + n0 (j + n1 k) */
   double lower[3], upper[3];
+  const double* nodes[3];     /* with OR_QP_GRID_GRADED: per-axis breakpoints [n[a]+1] (rectilinear grid); NULL =
+                                 that axis equidistant on [lower, upper] */
 } or_qp_grid_t;
 
 typedef struct {

@@ -4,8 +4,10 @@
  * 3d) over small meshes, every coefficient and tensor kind and both boundary kinds.  A memory error in the
  * checker would silently corrupt every parity claim.  Built and run by tests/test_host_sanitizers.py. */
 #include <math.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "swipdg_oracle.h"
 #include "swipdg_oracle_qp.h"
@@ -183,6 +185,63 @@ static void exercise_qp(int dim, int p, int nx, int ny, int nz)
   free(pe); free(rp); free(col); free(val);
 }
 
+/* graded (rectilinear) 3d grid: per-axis breakpoints of exactly n[a]+1 heap doubles, so that a read past either
+ * end of a node array is caught; assemble / rhs / product (the penalty product reads both sides of a face) */
+static void exercise_qp_graded(int p)
+{
+  const int n[3] = {4, 3, 2};
+  const double w[3][4] = {{1.0, 1.7, 2.89, 4.913}, {1.0, 3.0, 1.0, 0}, {2.0, 1.0, 0, 0}};
+  double* nodes[3];
+  for (int a = 0; a < 3; ++a) {
+    nodes[a] = malloc(sizeof(double) * (n[a] + 1));
+    nodes[a][0] = -0.5 * a;
+    for (int i = 0; i < n[a]; ++i) nodes[a][i + 1] = nodes[a][i] + 0.25 * w[a][i];
+  }
+  or_qp_grid_t g = {3 | OR_QP_GRID_GRADED, p, {n[0], n[1], n[2]}, {0, 0, 0}, {1, 1, 1}, {nodes[0], nodes[1], nodes[2]}};
+  const int64_t ne = or_qp_num_elements(&g);
+  const int nb = (p + 1) * (p + 1) * (p + 1);
+  const int64_t nnz = or_qp_pattern_nnz(&g);
+  int64_t* rp = malloc(sizeof(int64_t) * (ne * nb + 1));
+  int32_t* col = malloc(sizeof(int32_t) * nnz);
+  double* val = malloc(sizeof(double) * nnz);
+  double* b = malloc(sizeof(double) * ne * nb);
+  double* pe = malloc(sizeof(double) * ne);
+  for (int64_t e = 0; e < ne; ++e) pe[e] = 0.5 + (double)(e % 7);
+  CHECK(or_qp_pattern(&g, NULL, rp, col) == 0 && rp[ne * nb] == nnz);
+  or_qp_scalar_t kap = {OR_QP_FN_PER_ELEM, 0, 0, 0, 0, 0, pe};
+  or_qp_scalar_t one = {OR_QP_FN_CONST, 0, 1.0, 0, 0, 0, NULL};
+  or_qp_tensor_t ten = {OR_QP_TENSOR_CONST, 0, {1, 0, 0, 1, 0, 1}, NULL};
+  or_qp_params_t prm = {20.0, 38.0, 0.5, OR_QP_BOUNDARY_DIRICHLET, -1, -1, 0};
+  CHECK(or_qp_assemble(&g, &kap, &ten, &prm, NULL, rp, col, val) == 0 && finite_all(val, nnz));
+  CHECK(or_qp_rhs_swipdg(&g, NULL, &kap, &ten, &one, NULL, &prm, NULL, b) == 0 && finite_all(b, ne * nb));
+  /* A.1 = b(g_D = 1): holds on a graded grid only if every face sees both sides' own geometry */
+  double bmax = 0.0, dmax = 0.0;
+  for (int64_t r = 0; r < ne * nb; ++r) {
+    double s = 0.0;
+    for (int64_t q = rp[r]; q < rp[r + 1]; ++q) s += val[q];
+    if (fabs(b[r]) > bmax) bmax = fabs(b[r]);
+    if (fabs(s - b[r]) > dmax) dmax = fabs(s - b[r]);
+  }
+  CHECK(bmax > 0.0 && dmax <= 1e-12 * bmax);
+  CHECK(or_qp_product(&g, OR_PRODUCT_PENALTY, &kap, &ten, &prm, NULL, rp, col, val) == 0 && finite_all(val, nnz));
+  /* a caller that still passes the earlier struct (it ended after `upper`): without OR_QP_GRID_GRADED the
+   * library must not read `nodes`.  The grid lives in a heap block of exactly the earlier size, so a read past
+   * it is caught; the values are the equidistant ones. */
+  or_qp_grid_t eq = {3, p, {n[0], n[1], n[2]}, {0, 0, 0}, {1, 1, 1}, {NULL, NULL, NULL}};
+  or_qp_grid_t* old = malloc(offsetof(or_qp_grid_t, nodes));
+  memcpy(old, &eq, offsetof(or_qp_grid_t, nodes));
+  double* val2 = malloc(sizeof(double) * nnz);
+  CHECK(or_qp_num_elements(old) == ne && or_qp_pattern_nnz(old) == nnz);
+  CHECK(or_qp_assemble(old, &kap, &ten, &prm, NULL, rp, col, val) == 0);
+  CHECK(or_qp_assemble(&eq, &kap, &ten, &prm, NULL, rp, col, val2) == 0);
+  CHECK(memcmp(val, val2, sizeof(double) * nnz) == 0);
+  CHECK(or_qp_rhs_swipdg(old, NULL, &kap, &ten, &one, NULL, &prm, NULL, b) == 0 && finite_all(b, ne * nb));
+  CHECK(or_qp_product(old, OR_PRODUCT_PENALTY, &kap, &ten, &prm, NULL, rp, col, val) == 0 && finite_all(val, nnz));
+  free(old); free(val2);
+  free(pe); free(b); free(rp); free(col); free(val);
+  for (int a = 0; a < 3; ++a) free(nodes[a]);
+}
+
 int main(void)
 {
   double x[512], w[256];
@@ -197,6 +256,7 @@ int main(void)
   for (int p = 1; p <= 3; ++p) {
     exercise_qp(2, p, 4, 3, 1);
     exercise_qp(3, p, 3, 2, 2);
+    exercise_qp_graded(p);
   }
   if (failures) {
     fprintf(stderr, "%d check(s) failed\n", failures);

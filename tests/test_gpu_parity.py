@@ -383,6 +383,47 @@ def test_parallelogram_mesh_uniform_tiles(ctx, smooth):
 
 
 @pytest.mark.parametrize("smooth", [False, True])
+def test_graded_rectilinear_q1_full_tiles(ctx, smooth):
+    """Q1 on a 70 x 30 rectilinear grid with graded x and y breakpoints: full 64-element interior tiles whose
+    face neighbours differ in size (every other Q1 mesh of this file consists of congruent parallelograms, on
+    which the neighbour's geometry equals the element's own).  Widths cycle through ratios up to 3."""
+    torch = _torch()
+    nx, ny = 70, 30
+    wx = np.array([1.0, 3.0, 1.5, 2.0, 0.75])[np.arange(nx) % 5] * 1.01 ** np.arange(nx)
+    wy = np.array([2.0, 1.0, 3.0])[np.arange(ny) % 3] * 0.98 ** np.arange(ny)
+    xs = np.concatenate([[0.0], np.cumsum(wx)]) * (5.0 / wx.sum())
+    ys = np.concatenate([[0.0], np.cumsum(wy)]) * (1.0 / wy.sum()) - 0.25
+    et, _, ev = O.cube_grid(nx, ny)
+    X, Y = np.meshgrid(xs, ys)
+    coords = np.stack([X.ravel(), Y.ravel()], axis=1).copy()
+    grid = H.Grid.from_connectivity(H.CUBE, coords, ev)
+    rng = np.random.default_rng(17)
+    ne = ev.shape[0]
+    a = rng.uniform(0.5, 2.0, ne); c = rng.uniform(0.5, 2.0, ne); b = rng.uniform(-0.3, 0.3, ne)
+    sym = np.stack([a, b, c], 0)
+    if smooth:
+        fns = [H.scalar_fn(H.FN_SINUSOID, 1.0, 0.75, 4 * np.pi, 2 * np.pi, order=3)]
+        ofn = O.scalar(O.FN_SINUSOID, 1.0, 0.75, 4 * np.pi, 2 * np.pi, order=3)
+    else:
+        kap = rng.uniform(0.1, 10.0, ne)
+        fns = [H.scalar_fn(H.FN_PER_ELEM, per_elem=torch.from_numpy(kap).cuda())]
+        ofn = O.scalar(O.FN_PER_ELEM, per_elem=kap)
+    tsym = torch.from_numpy(np.ascontiguousarray(sym)).cuda()
+    local, (rp, col, _), (val,) = _run_product(ctx, grid, fns, H.tensor_fn(H.TENSOR_SYM_PER_ELEM, per_elem=tsym))
+    assert np.array_equal(local.global_id, np.arange(ne))          # no subdomains: element order kept
+    nb = local.neighbors[:, local.own_begin:local.own_end]
+    full = (nb >= 0).all(axis=0)[: (local.n_own // 64) * 64].reshape(-1, 64).all(axis=1)
+    assert full.any() and not full.all(), "expected both uniform and boundary tiles"
+    og = O.Grid(et, coords, ev)
+    orp, ocol, oval = O.assemble(og, ofn, O.tensor(O.TENSOR_SYM_PER_ELEM, per_elem=np.ascontiguousarray(sym.T)),
+                                 O.params())
+    assert np.array_equal(rp, orp) and np.array_equal(col, ocol)
+    worst, ok = compare_rows(rp, val, oval, RTOL)
+    print("graded Q1 smooth=%s worst row rel diff %.3g" % (smooth, worst))
+    assert ok, worst
+
+
+@pytest.mark.parametrize("smooth", [False, True])
 def test_scrambled_quad_orientations(ctx, smooth):
     """Q1 closed-form / quadrature policies against the oracle when faces meet under all twin-face ids and
     reversals (the role-slot mapping), with full tiles (padded image) present."""
