@@ -15,7 +15,7 @@ int set_error(int code, const std::string& msg);
 int ctx_device(const hdd_ctx* ctx);   // HIP device ordinal a context is bound to
 }  // namespace hdd
 
-// Sharded-step fixup off the assembly stream (abi_assemble.hip, used by shard.hip): the element-list pass into side
+// Sharded-step fixup off the assembly stream (abi_assemble.hip, used by shard_step.hip): the element-list pass into side
 // buffers of hdd_fix_rb(elem_type) doubles per listed element (n + 1 slots per component), and the copy of those
 // row blocks into the value arrays.
 int hdd_fix_rb(int32_t elem_type);

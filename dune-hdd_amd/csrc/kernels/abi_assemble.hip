@@ -1,5 +1,5 @@
 // dune-hdd_amd/csrc/kernels/abi_assemble.hip -- C ABI: SWIPDG assembly dispatch (2d tile driver and HDD_HEX) and the
-// sharded step's fixup entry points (hdd_internal.hh, used by shard.hip)
+// sharded step's fixup entry points (hdd_internal.hh, used by shard_step.hip)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -125,7 +125,7 @@ static int assemble_impl(hdd_ctx* ctx, const hdd_mesh* m, const hdd_scalar_fn* k
   // hdd_last_tile_kernel names the kernel THIS call launches (every launch path sets it); an element-list pass (the
   // sharded step's side pass beside its tile launch) leaves the tile launch's name in place
   if (mode.list_kind == LIST_TILES) hdd::last_tile_kernel_slot() = "";
-  // The sharded step (shard.hip) runs this function on two streams at once with one context: the element-list
+  // The sharded step (shard_step.hip) runs this function on two streams at once with one context: the element-list
   // pass on the transfer stream beside the SKIP launch on the caller's stream.  That is safe only because the
   // 2d paths below (tiles, element lists, skip_ghost) use no context workspace (ws / scan_ws / rhs_ws); the
   // one path that does (HDD_HEX, p = 3) takes no lists, and the sharded step runs it exchange-then-assemble.
@@ -226,7 +226,7 @@ extern "C" int hdd_swipdg_assemble_elements(hdd_ctx* ctx, const hdd_mesh* m, con
 }
 
 // ------------------------------------------------------------------------------------------------
-// Sharded-step fixup off the assembly stream (shard.hip): the element-list pass writes each listed element's row
+// Sharded-step fixup off the assembly stream (shard_step.hip): the element-list pass writes each listed element's row
 // block into a side buffer (slot fix_rb(m) doubles, one buffer of n + 1 slots per component) on the transfer
 // stream while the full-range assembly runs; after the join, fix_scatter_kernel copies the blocks into place.
 // ------------------------------------------------------------------------------------------------

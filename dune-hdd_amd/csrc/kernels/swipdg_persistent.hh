@@ -705,7 +705,7 @@ __global__ void __launch_bounds__(64) swipdg_elements_kernel(const AssembleArgs 
 }
 
 // Element-list pass without LDS, so that it runs on the transfer stream beside a persistent assembly that holds
-// the LDS (sharded step, shard.hip).  LIST_IN_PLACE: lane i writes the row block of listed element i in
+// the LDS (sharded step, shard_step.hip).  LIST_IN_PLACE: lane i writes the row block of listed element i in
 // place (the concurrent assembly runs with a.skip_ghost and leaves those blocks alone; inactive lanes repeat
 // lane 0's element); LIST_SIDE_BUFFER: into side buffers a.vals[c] + i RB (slot n: the inactive lanes' dummy), which
 // fix_scatter_kernel copies into place after the join (round-3 A/B variant).

@@ -1,8 +1,10 @@
 // Host-side sanitizer driver (AddressSanitizer + UndefinedBehaviorSanitizer) for the product's host code: the
 // grid providers, rank-local views, halo plans, coefficient lookups, CSR pattern builders and block-operator maps
 // of csrc/host/grid.cpp, called through the C ABI (include/hdd.h) over a sweep of sizes, partitions, element types,
-// boundary kinds and the documented error paths; and the quadrature rules of csrc/host/quadrature.cpp.  GPU code is out of reach of the sanitizers on this pool; this
-// covers everything the library runs on the host.  Built and run by tests/test_host_sanitizers.py.
+// boundary kinds and the documented error paths; the quadrature rules of csrc/host/quadrature.cpp; and the sharded
+// step's schedule plan (csrc/host/shard_plan.hh) against its documented truth table.  GPU code is out of reach of
+// the sanitizers on this pool; this covers everything the library runs on the host.  Built and run by
+// tests/test_host_sanitizers.py.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -11,6 +13,7 @@
 
 #include "hdd.h"
 #include "quadrature.hh"
+#include "shard_plan.hh"
 
 static int failures = 0;
 #define CHECK(cond)                                                            \
@@ -260,9 +263,106 @@ static void exercise_quadrature()
   }
 }
 
+// The sharded step's schedule (csrc/host/shard_plan.hh) against what include/hdd.h's HDD_SHARD_* comments and
+// DESIGN.md §5 promise.  The rows are written from those documents, not from the plan function.  Unless a row says otherwise:
+// a transfer, a stream-based communicator, interior tiles, ghost-adjacent elements, closed-form kappa, release build.
+static void exercise_step_plan()
+{
+  using namespace hdd;
+  const uint32_t INLINE = HDD_SHARD_FIX_INLINE, SCATTER = HDD_SHARD_FIX_SCATTER, INPLACE = HDD_SHARD_FIX_INPLACE,
+                 SPLIT = HDD_SHARD_SPLIT_TILES, LAST = HDD_SHARD_LAUNCH_LAST;
+  auto facts = [](int32_t et, int32_t peers, uint32_t flags) {
+    return StepFacts{et, peers, 5, 7, flags, true, CommKind::Stream, true, false};
+  };
+  auto plan = [&](int32_t et, int32_t peers, uint32_t flags) { return plan_step(facts(et, peers, flags)); };
+  const int32_t P1 = HDD_SIMPLEX, Q1 = HDD_CUBE;
+  {   // P1, one peer: in place on the transfer stream, the SKIP launch first
+    const StepPlan p = plan(P1, 1, 0);
+    CHECK(p.schedule == Schedule::FixInPlace && p.pack_on == PackOn::Transfer && p.tiles_first && !p.pack_first &&
+          !p.direct);
+  }
+  {   // P1, two peers: the tile split, its pack on `stream`
+    const StepPlan p = plan(P1, 2, 0);
+    CHECK(p.schedule == Schedule::SplitTiles && p.pack_on == PackOn::Stream && !p.tiles_first && !p.direct);
+    StepFacts f = facts(P1, 2, 0);
+    f.n_in = 0;   // nothing to split off
+    CHECK(plan_step(f).schedule == Schedule::FixInPlace);
+    f.flags = SPLIT;   // asked for all the same: nothing overlaps
+    CHECK(plan_step(f).schedule == Schedule::Serial);
+  }
+  for (int32_t peers = 1; peers <= 3; ++peers) {   // Q1: serial by default, RCCL straight on `stream`
+    const StepPlan p = plan(Q1, peers, 0);
+    CHECK(p.schedule == Schedule::Serial && p.direct && p.pack_on == PackOn::Stream && !p.pack_first && !p.tiles_first);
+  }
+  {   // Q1, in place: the pack on `stream` ahead of the SKIP launch
+    const StepPlan p = plan(Q1, 1, INPLACE);
+    CHECK(p.schedule == Schedule::FixInPlace && p.pack_first && p.tiles_first && p.pack_on == PackOn::Transfer);
+  }
+  {   // the side buffers: value-major for the closed-form Q1 policy (reserve launch first), row blocks otherwise
+    const StepPlan p = plan(Q1, 1, SCATTER);
+    CHECK(p.schedule == Schedule::FixSoa && p.tiles_first && p.fix_buffer());
+    StepFacts f = facts(Q1, 1, SCATTER);
+    f.kappa_closed_form = false;
+    const StepPlan smooth = plan_step(f);
+    CHECK(smooth.schedule == Schedule::FixRowBlocks && !smooth.tiles_first && smooth.fix_buffer());
+    const StepPlan p1 = plan(P1, 1, SCATTER);
+    CHECK(p1.schedule == Schedule::FixRowBlocks && !p1.tiles_first && p1.fix_buffer());
+    CHECK(!plan(P1, 1, INPLACE).fix_buffer() && !plan(P1, 1, INLINE).fix_buffer());
+  }
+  CHECK(plan(Q1, 1, SPLIT).schedule == Schedule::SplitTiles);
+  for (int32_t et : {P1, Q1}) {
+    CHECK(plan(et, 1, INLINE).schedule == Schedule::FixInline);
+    CHECK(plan(et, 2, INLINE | INPLACE).schedule == Schedule::FixInline);
+    CHECK(plan(et, 2, INPLACE | SCATTER).schedule == Schedule::FixInPlace);
+    for (uint32_t fix : {INLINE, SCATTER, INPLACE}) {
+      CHECK(plan(et, 2, SPLIT | fix).schedule == Schedule::SplitTiles);
+      StepFacts f = facts(et, 2, fix);
+      f.n_fix = 0;   // no ghost-adjacent element: nothing to fix up off the stream
+      const StepPlan p = plan_step(f);
+      CHECK(p.schedule == Schedule::FixInline && !p.tiles_first && !p.off_stream_fix());
+    }
+  }
+  for (uint32_t flags = 0; flags < 512; ++flags) {
+    if (flags & HDD_SHARD_NO_HALO) continue;   // no exchange, no plan
+    for (int32_t peers = 1; peers <= 3; ++peers) {
+      CHECK(plan(HDD_HEX, peers, flags).schedule == Schedule::Serial);   // no lists for hexahedra
+      for (int32_t et : {P1, Q1, int32_t(HDD_HEX)}) {
+        const StepPlan p = plan(et, peers, flags | HDD_SHARD_NO_OVERLAP);
+        CHECK(p.schedule == Schedule::Serial && p.direct && p.pack_on == PackOn::Stream && !p.tiles_first);
+        // the release build ignores HDD_SHARD_LAUNCH_LAST
+        const StepPlan a = plan(et, peers, flags | LAST), b = plan(et, peers, flags & ~LAST);
+        CHECK(a.schedule == b.schedule && a.pack_on == b.pack_on && a.pack_first == b.pack_first &&
+              a.tiles_first == b.tiles_first && a.direct == b.direct);
+      }
+    }
+  }
+  {   // ... an ablation build does not: round 3's order
+    StepFacts f = facts(P1, 1, LAST);
+    f.ablation = true;
+    const StepPlan p = plan_step(f);
+    CHECK(p.schedule == Schedule::FixInPlace && !p.tiles_first);
+    f.flags = 0;
+    CHECK(plan_step(f).tiles_first);
+  }
+  // a side schedule without a transfer stream to borrow: the host transport, the loopback study
+  for (uint32_t fix : {0u, INLINE, SCATTER, INPLACE}) {
+    StepFacts f = facts(P1, 1, fix);
+    f.comm = CommKind::Host;
+    CHECK(plan_step(f).pack_on == PackOn::Side && plan_step(f).side_stream());
+    for (CommKind k : {CommKind::None, CommKind::Host, CommKind::Stream}) {
+      f.comm = k;
+      f.flags = fix | HDD_SHARD_NO_TRANSFER;
+      f.transfer = false;
+      CHECK(plan_step(f).pack_on == PackOn::Side);
+    }
+    CHECK(!plan(P1, 1, fix).side_stream() && plan(P1, 1, fix).pack_on == PackOn::Transfer);
+  }
+}
+
 int main()
 {
   exercise_quadrature();
+  exercise_step_plan();
   // 2d structured: element types, ragged sizes, partitions, boundary kinds
   const int sizes[][4] = {{1, 1, 1, 1}, {9, 1, 1, 1}, {1, 9, 1, 1}, {16, 16, 1, 1}, {33, 17, 2, 2},
                           {65, 2, 4, 1},  {12, 8, 3, 1}, {24, 16, 4, 4}, {7, 5, 7, 5}};

@@ -3,9 +3,9 @@
 
 Over RCCL the step packs on the communicator's transfer stream, posts the group send/recv there, computes the
 ghost-adjacent elements on that stream right behind the receives and joins it by an event
-(shard.hip: ps = comm->xfer, the fixup on ps, hdd_comm_wait's event join).  The device transport takes exactly
-that branch -- only the ncclSend/ncclRecv pair is replaced by (wait for the source's packed event, hipMemcpyAsync,
-record "copied"; the completion waits for every destination's "copied") -- so these tests execute the stream /
+(shard_plan.hh: PackOn::Transfer; shard_step.hip: ps = comm->xfer, the fixup on ps, hdd_comm_wait's event join).
+The device transport takes exactly that branch -- only the ncclSend/ncclRecv pair is replaced by
+(wait for the source's packed event, hipMemcpyAsync, record "copied"; the completion waits for every destination's "copied") -- so these tests execute the stream /
 event schedule the driver's 8-GPU run uses, which no host-transport test reaches.
 
 Reference semantics: block-swipdg.hh:355-382 (the owner of ss writes A_ss and A_ss,nn), SURVEY.md 8(e).
