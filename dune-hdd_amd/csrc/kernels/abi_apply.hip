@@ -7,11 +7,13 @@
 #include <algorithm>
 #include <cstdint>
 
-#include "abi_common.hh"
-#include "apply_kernels.hh"
+#include "apply_plan.hh"
 
 using hdd::set_error;
+using hdd::abi::ApplyPlan;
 using hdd::abi::fail;
+using hdd::abi::plan_apply;
+using hdd::abi::run_apply;
 namespace dev = hdd::dev;
 
 namespace {
@@ -20,17 +22,9 @@ const char*& last_apply_kernel_slot()
   thread_local const char* name = "";
   return name;
 }
+}  // namespace
 
-struct ApplyPlan {
-  dev::ApplyArgs a;
-  bool tile;
-  int nb, nf;        // tile path
-  bool short_rows;   // generic path: a group of 8 lanes per row instead of a wave
-};
-
-// Every check of hdd_operator_apply's operator arguments (no device call, nothing dereferenced but host structs);
-// fills the plan except x / y.
-int plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+int hdd::abi::plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
                int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P)
 {
   if (!ctx || !pattern || !d_vals) return fail(HDD_ERR_INVALID, who, "null argument");
@@ -93,15 +87,13 @@ int plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_cs
   return HDD_OK;
 }
 
+namespace {
 template <int NB, int NF>
 hipError_t launch_tile(const hdd_ctx* ctx, const dev::ApplyArgs& a, bool multi, hipStream_t s)
 {
   using I = dev::ApplyImage<NB, NF>;
   const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
-  // as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB); tile_range wants a multiple of 8 workgroups
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / I::BYTES));
-  int64_t G = std::max<int64_t>(8, (int64_t(ctx->n_cu) * per_cu) & ~int64_t(7));
-  if (G >= n_tiles) G = n_tiles;
+  const int64_t G = hdd::abi::apply_tile_grid<NB, NF>(ctx, n_tiles);
   static const char* names[2] = {NB == 3 ? "apply_tile_kernel<3, 3, 1>" : "apply_tile_kernel<4, 4, 1>",
                                  NB == 3 ? "apply_tile_kernel<3, 3, 4>" : "apply_tile_kernel<4, 4, 4>"};
   last_apply_kernel_slot() = names[multi];
@@ -115,9 +107,7 @@ hipError_t launch_tile(const hdd_ctx* ctx, const dev::ApplyArgs& a, bool multi, 
 template <int G>
 hipError_t launch_csr(const dev::ApplyArgs& a, bool multi, hipStream_t s)
 {
-  const int64_t n_rows = a.row_end - a.row_begin;
-  const int64_t per_wg = 256 / G;
-  const unsigned grid = unsigned(std::min<int64_t>((n_rows + per_wg - 1) / per_wg, 256 * 64));
+  const unsigned grid = unsigned(hdd::abi::apply_csr_grid<G>(a.row_end - a.row_begin));
   static const char* names[2] = {G == 8 ? "apply_csr_kernel<8, 1>" : "apply_csr_kernel<64, 1>",
                                  G == 8 ? "apply_csr_kernel<8, 4>" : "apply_csr_kernel<64, 4>"};
   last_apply_kernel_slot() = names[multi];
@@ -126,8 +116,9 @@ hipError_t launch_csr(const dev::ApplyArgs& a, bool multi, hipStream_t s)
   return hipGetLastError();
 }
 
-// the launches of a checked plan: the values are read once per group of APPLY_NV vectors
-int run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
+}  // namespace
+
+int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
               int32_t n_vec, void* stream)
 {
   if (P.a.row_end == P.a.row_begin) return HDD_OK;
@@ -148,7 +139,6 @@ int run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, in
   }
   return HDD_OK;
 }
-}  // namespace
 
 extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot(); }
 

@@ -17,6 +17,10 @@
 // apply_csr_kernel -- plain CSR on row_ptr / col for everything else; a group of G lanes per row (8 for the short
 //   rows of P1 / Q1 / volume patterns, a wave for the hexahedral Q_p rows), shuffle reduction in a fixed order.
 // apply2_partial_kernel / apply2_final_kernel -- out[i][j] = v_i . w_j in two deterministic stages.
+// DOT variants (NV = 1, a square diagonal range: x and y share their numbering) also leave x . y behind, for the
+//   conjugate gradient iteration: every lane adds x_r y_r of its own rows over its tiles / rows in order, the
+//   workgroup reduces once at the end (shuffle tree, then the waves in order) and writes partial[blockIdx].  The
+//   instantiations without DOT are unchanged by it (same registers).
 // No atomics anywhere: results are bit-identical from call to call.
 #pragma once
 #include <cstdint>
@@ -47,6 +51,11 @@ struct ApplyArgs {
   int64_t ldx;
   double* y;                           // y[v * ldy + row - row_begin]
   int64_t ldy;
+  // DOT variants only (hdd_operator_solve, solve_kernels.hh): partial[blockIdx] = this workgroup's share of x . y, and
+  // the iteration's stop word -- the launch returns at once when *done_at <= iteration
+  double* partial;
+  const int32_t* done_at;
+  int32_t iteration;
 };
 
 // sizes of the tile kernel's LDS image: 16-byte chunks per lane (odd row blocks, P1: the image origin may lie one
@@ -79,13 +88,17 @@ __device__ __forceinline__ int64_t apply_uni64(int64_t v)
 // whole to c ^ ((c >> 4) & 15), so the staging writes stay aligned and conflict-free.
 __device__ __forceinline__ int apply_swz(int p) { return p ^ (((p >> 5) & 15) << 1); }
 
-template <int NB, int NF, int NV>
+template <int NB, int NF, int NV, bool DOT = false>
 __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
 {
+  static_assert(!DOT || NV == 1, "the dot product is that of one vector");
   using I = ApplyImage<NB, NF>;
   constexpr int CH = I::CHUNKS, U = I::U;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int lane = threadIdx.x;
+  double dot = 0.0;   // DOT: this lane's x . y over its elements, in tile order
+  if constexpr (DOT)
+    if (*a.done_at <= a.iteration) return;   // (wave-uniform)
   const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
   const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
   __amdgpu_buffer_rsrc_t xr[NV];
@@ -159,6 +172,7 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       }
     const int rl = NB * (nint + 1);   // row length
     double acc[NV][NB];
+    [[maybe_unused]] double xown[NB] = {};
 #pragma unroll
     for (int v = 0; v < NV; ++v)
 #pragma unroll
@@ -172,6 +186,10 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       for (int v = 0; v < NV; ++v)
 #pragma unroll
         for (int j = 0; j < NB; ++j) xv[v][j] = v < a.nv ? ld64f(xr[v], xo + 8u * j) : 0.0;
+      if constexpr (DOT)   // the element's own block is one of the gathered ones: these are its rows of x
+        if (id[b] == int(e))
+#pragma unroll
+          for (int j = 0; j < NB; ++j) xown[j] = xv[0][j];
 #pragma unroll
       for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -187,13 +205,25 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       if (v < a.nv)
 #pragma unroll
         for (int i = 0; i < NB; ++i) yo[v * a.ldy + i] = acc[v][i];
+    if constexpr (DOT)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) dot = __builtin_fma(xown[i], acc[0][i], dot);
+  }
+  if constexpr (DOT) {   // every lane is back here, whatever its tiles were
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) dot += __shfl_xor(dot, d, 64);
+    if (lane == 0) a.partial[blockIdx.x] = dot;
   }
 }
 
 // G lanes per row, 256 / G rows per workgroup pass
-template <int G, int NV>
+template <int G, int NV, bool DOT = false>
 __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
 {
+  static_assert(!DOT || NV == 1, "the dot product is that of one vector");
+  double dot = 0.0;   // DOT: the group leaders' x_r y_r over their rows, in row order
+  if constexpr (DOT)
+    if (*a.done_at <= a.iteration) return;   // (uniform)
   const int gl = threadIdx.x % G;
   const int64_t n_rows = a.row_end - a.row_begin;
   const int64_t stride = int64_t(gridDim.x) * (256 / G);
@@ -222,12 +252,22 @@ __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
         if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
+    if constexpr (DOT)
+      if (gl == 0) dot = __builtin_fma(a.x[rr], acc[0], dot);   // square diagonal range: row rr is column rr
+  }
+  if constexpr (DOT) {
+    __shared__ double red[4];
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) dot += __shfl_xor(dot, d, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dot;
+    __syncthreads();
+    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
   }
 }
 
 // apply2, stage 1: partial[block][i * HDD_MAX_VEC + j] = sum over the block's rows of v_i[r] w_j[r] (fixed row ->
 // thread assignment, shuffle tree, then the four waves in order)
-__global__ void __launch_bounds__(256) apply2_partial_kernel(const double* v, int64_t ldv, int n_v, const double* w,
+[[maybe_unused]] static __global__ void __launch_bounds__(256) apply2_partial_kernel(const double* v, int64_t ldv, int n_v, const double* w,
                                                              int64_t ldw, int n_u, int64_t n, double* partial)
 {
   __shared__ double red[4][APPLY2_PAIRS];
@@ -266,7 +306,7 @@ __global__ void __launch_bounds__(256) apply2_partial_kernel(const double* v, in
 }
 
 // stage 2: out[i * n_u + j] = the blocks' partial sums, in block order
-__global__ void __launch_bounds__(64) apply2_final_kernel(const double* partial, int n_blocks, int n_v, int n_u, double* out)
+[[maybe_unused]] static __global__ void __launch_bounds__(64) apply2_final_kernel(const double* partial, int n_blocks, int n_v, int n_u, double* out)
 {
   const int p = threadIdx.x, i = p / HDD_MAX_VEC, j = p % HDD_MAX_VEC;
   if (i >= n_v || j >= n_u) return;

@@ -77,12 +77,14 @@ struct hdd_ctx {
   hipEvent_t rhs_evt = nullptr;       //   a call on another stream waits for it (the list is shared state)
   bool rhs_used = false;
   double* apply2_ws = nullptr;   // hdd_operator_apply2's partial sums, allocated with the context (the call allocates nothing)
+  double* solve_state_h = nullptr;   // hdd_operator_solve: 64 pinned host bytes its device state is read back into
 
   // the scratch buffers release themselves; what is left are the plain members
   ~hdd_ctx()
   {
     if (q3g_tab) (void)hipFree(q3g_tab);
     if (apply2_ws) (void)hipFree(apply2_ws);
+    if (solve_state_h) (void)hipHostFree(solve_state_h);
     if (nnz_h) (void)hipHostFree(nnz_h);
     if (rhs_evt) (void)hipEventDestroy(rhs_evt);
     if (ops_evt) (void)hipEventDestroy(ops_evt);

@@ -1,0 +1,375 @@
+// dune-hdd_amd/csrc/kernels/solve_kernels.hh -- preconditioned conjugate gradients on sum_q theta_q A_q
+// (hdd_operator_solve, abi_solve.hip): what ContainerBasedDefault::uncached_solve's apply_inverse does (base.hh:327-367).
+//
+// One iteration k is three launches, ordered by the stream alone (no atomics, no grid barriers, no flags between
+// workgroups of a launch):
+//   apply_*_kernel<..., DOT>  q = A p, partial_pq[workgroup] (apply_kernels.hh)
+//   cg_update_kernel<BS>      every wave sums partial_pq in the same order (same bits everywhere), alpha = rho / p.q;
+//                             one lane owns one block of BS rows: x += alpha p, r -= alpha q, z = D^-1 r; partials of
+//                             r.z and r.r per workgroup
+//   cg_direction_kernel       sums the partials, beta = rho' / rho, p = z + beta p; one lane of workgroup 0 writes
+//                             the state and history[k + 1]
+// The state (SolveState) lives in the caller's workspace.  rho is double-buffered by the parity of k and the stop word
+// done_at is the iteration count at which the solve ended (INT32_MAX while running): the workgroups of launch k that
+// read the state while workgroup 0 writes it decide the same either way (done_at <= k is false for the old and for
+// the new value k + 1; a breakdown is detected by every workgroup from the same sums).  A launch of iteration k
+// returns at once when done_at <= k, so the host may enqueue any number of iterations between two looks.
+// Every sum is two-stage in a fixed order: bit-identical from call to call, and independent of check_every.
+// The build has -ffinite-math-only: non-finite scalars are recognised by their bits, behind an optimisation barrier
+// (solve_finite).
+#pragma once
+#include <cstdint>
+
+#include "apply_kernels.hh"
+
+namespace hdd {
+namespace dev {
+
+constexpr int SOLVE_PARTS = 4096;    // most partial sums of one kind (workgroups of the launch that wrote them)
+constexpr int SOLVE_FLAG_ZERO_RHS = 1;
+
+struct SolveState {
+  double rho[2];       // r . z, indexed by the parity of the iteration that reads it
+  double rr, bb;       // ||r||^2 (recurrence), ||b||^2
+  double thresh2;      // max(rtol ||b||, atol)^2
+  int32_t iteration, status, done_at, flags;
+  double pad;
+};
+static_assert(sizeof(SolveState) == 64, "eight doubles of the workspace");
+
+struct SolveVectors {
+  SolveState* state;
+  double *x, *p, *q, *r, *z;            // z == r without a preconditioner
+  const double* dinv;                   // [n_blocks][BS (BS + 1) / 2], the lower triangles of the inverse blocks
+  double *part_pq, *part_rz, *part_rr, *part_bb;
+  int64_t n;                            // rows
+  int32_t n_pq;                         // partial sums the DOT apply wrote
+  double* history;                      // nullable
+};
+
+__device__ __forceinline__ bool solve_finite(double v)
+{
+  uint64_t u = uint64_t(__double_as_longlong(v));
+  asm volatile("" : "+v"(u));   // opaque: under -ffinite-math-only the test on the bits would be folded to true
+  return ((u >> 52) & 0x7ff) != 0x7ff;
+}
+
+// sum of part[0, n) by one wave, lane l the entries l, l + 64, ... in order, then a butterfly: every lane of every
+// wave that calls it gets the same bits
+__device__ __forceinline__ double solve_wave_sum(const double* part, int n)
+{
+  double s = 0.0;
+  for (int i = threadIdx.x & 63; i < n; i += 64) s += part[i];
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+// the workgroup's sum of one value per thread (256 threads): butterfly, then the four waves in order; thread 0 has it
+__device__ __forceinline__ double solve_block_sum(double s, double* red)
+{
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+template <int BS>
+constexpr int solve_packed() { return BS * (BS + 1) / 2; }
+
+// BS consecutive doubles; A16: BS is even and the address 16-byte aligned
+template <int BS, bool A16>
+__device__ __forceinline__ void solve_load(const double* p, double (&v)[BS])
+{
+  if constexpr (A16) {
+#pragma unroll
+    for (int i = 0; i < BS; i += 2) {
+      const dvec2 t = *reinterpret_cast<const dvec2*>(p + i);
+      v[i] = t.x;
+      v[i + 1] = t.y;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < BS; ++i) v[i] = p[i];
+  }
+}
+template <int BS, bool A16>
+__device__ __forceinline__ void solve_store(double* p, const double (&v)[BS])
+{
+  if constexpr (A16) {
+#pragma unroll
+    for (int i = 0; i < BS; i += 2) {
+      dvec2 t;
+      t.x = v[i];
+      t.y = v[i + 1];
+      *reinterpret_cast<dvec2*>(p + i) = t;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < BS; ++i) p[i] = v[i];
+  }
+}
+
+// z = D^-1 r from the packed lower triangle of the (symmetric) inverse block
+template <int BS>
+__device__ __forceinline__ void solve_precond(const double* dinv, const double (&r)[BS], double (&z)[BS])
+{
+  double m[solve_packed<BS>()];
+#pragma unroll
+  for (int k = 0; k < solve_packed<BS>(); ++k) m[k] = dinv[k];
+#pragma unroll
+  for (int i = 0; i < BS; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) s = __builtin_fma(i >= j ? m[i * (i + 1) / 2 + j] : m[j * (j + 1) / 2 + i], r[j], s);
+    z[i] = s;
+  }
+}
+
+// In-place inverse of a symmetric positive definite block (Gauss-Jordan without pivoting: the pivots are the Schur
+// complements, positive for a definite block), packed lower triangle to out.  false: a pivot was not positive (or
+// not finite); out is then zero.
+template <int BS>
+__device__ __forceinline__ bool solve_invert(double (&A)[BS][BS], double* out)
+{
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < BS; ++k) {
+    const double piv = A[k][k];
+    ok = ok && solve_finite(piv) && piv > 0.0;
+    const double d = 1.0 / (ok ? piv : 1.0);
+    A[k][k] = 1.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) A[k][j] *= d;
+#pragma unroll
+    for (int i = 0; i < BS; ++i) {
+      if (i == k) continue;
+      const double f = A[i][k];
+      A[i][k] = 0.0;
+#pragma unroll
+      for (int j = 0; j < BS; ++j) A[i][j] = __builtin_fma(-f, A[k][j], A[i][j]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < BS; ++i)
+#pragma unroll
+    for (int j = 0; j <= i; ++j) {
+      const double v = 0.5 * (A[i][j] + A[j][i]);
+      out[i * (i + 1) / 2 + j] = ok && solve_finite(v) ? v : 0.0;
+    }
+  return ok;
+}
+
+// Diagonal blocks on the tile path (BS == NB): lane = element.  Its own block is block number (interior neighbours
+// with a smaller id) of its row block, whose row stride is NB (interior neighbours + 1) -- from elem_ptr and the
+// neighbours alone; col is not read.  part_bad[workgroup] = blocks that were not positive definite.
+template <int NB, int NF>
+__global__ void __launch_bounds__(256) solve_dinv_tile_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+{
+  __shared__ double red[4];
+  double bad = 0.0;
+  const int64_t n_el = a.e_end - a.e_begin;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_el; i += int64_t(gridDim.x) * 256) {
+    const int64_t e = a.e_begin + i;
+    int nint = 0, pos = 0;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      const int nb = a.nbrs[f * a.n_local + e];
+      nint += nb >= 0;
+      pos += nb >= 0 && nb < e;
+    }
+    const int rl = NB * (nint + 1);
+    int64_t base = a.elem_ptr[e - a.own_begin] + int64_t(pos) * NB;
+    double D[NB][NB];
+#pragma unroll
+    for (int r = 0; r < NB; ++r)
+#pragma unroll
+      for (int c = 0; c < NB; ++c) {
+        int64_t k = base + r * rl + c;
+        k = k < 0 ? 0 : (k >= a.nnz ? a.nnz - 1 : k);   // an index the mesh got wrong stays inside the arrays
+        double m = a.theta[0] * a.vals[0][k];
+        for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
+        D[r][c] = m;
+      }
+    if (!solve_invert<NB>(D, dinv + i * solve_packed<NB>())) bad += 1.0;
+  }
+  const double s = solve_block_sum(bad, red);
+  if (threadIdx.x == 0) part_bad[blockIdx.x] = s;
+}
+
+// Diagonal blocks on the CSR path: thread = block of BS rows, found in col
+template <int BS>
+__global__ void __launch_bounds__(256) solve_dinv_csr_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+{
+  __shared__ double red[4];
+  double bad = 0.0;
+  const int64_t n_blk = (a.row_end - a.row_begin) / BS;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+    const int64_t r0 = a.row_begin + i * BS;
+    double D[BS][BS];
+#pragma unroll
+    for (int r = 0; r < BS; ++r) {
+#pragma unroll
+      for (int c = 0; c < BS; ++c) D[r][c] = 0.0;
+      int64_t k0 = a.row_ptr[r0 + r], k1 = a.row_ptr[r0 + r + 1];
+      k0 = k0 < 0 ? 0 : k0;
+      k1 = k1 > a.nnz ? a.nnz : k1;
+      for (int64_t k = k0; k < k1; ++k) {
+        const int64_t c = int64_t(a.col[k]) - r0;
+        if (c < 0 || c >= BS) continue;
+        double m = a.theta[0] * a.vals[0][k];
+        for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
+#pragma unroll
+        for (int cc = 0; cc < BS; ++cc)
+          if (cc == c) D[r][cc] += m;
+      }
+    }
+    if (!solve_invert<BS>(D, dinv + i * solve_packed<BS>())) bad += 1.0;
+  }
+  const double s = solve_block_sum(bad, red);
+  if (threadIdx.x == 0) part_bad[blockIdx.x] = s;
+}
+
+// Setup: r = b (X0: b - q, q = A x0 from a plain apply), x = 0 (X0: kept), z = D^-1 r, p = z; partials of b.b, r.z, r.r
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_init_kernel(const SolveVectors v, const double* b, bool x0)
+{
+  __shared__ double red[3][4];
+  double bb = 0.0, rz = 0.0, rr = 0.0;
+  const int64_t n_blk = v.n / BS;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+    const int64_t o = i * BS;
+    double bv[BS], rv[BS], zv[BS];
+#pragma unroll
+    for (int k = 0; k < BS; ++k) bv[k] = b[o + k];   // the caller's b: no alignment assumed
+    if (x0) {
+      solve_load<BS, A16>(v.q + o, rv);
+#pragma unroll
+      for (int k = 0; k < BS; ++k) rv[k] = bv[k] - rv[k];
+    } else {
+#pragma unroll
+      for (int k = 0; k < BS; ++k) rv[k] = bv[k];
+      double zero[BS] = {};
+      solve_store<BS, A16>(v.x + o, zero);
+    }
+    if constexpr (PRE) solve_precond<BS>(v.dinv + i * solve_packed<BS>(), rv, zv);
+#pragma unroll
+    for (int k = 0; k < BS; ++k) {
+      if constexpr (!PRE) zv[k] = rv[k];
+      bb = __builtin_fma(bv[k], bv[k], bb);
+      rz = __builtin_fma(rv[k], zv[k], rz);
+      rr = __builtin_fma(rv[k], rv[k], rr);
+    }
+    solve_store<BS, A16>(v.r + o, rv);
+    if constexpr (PRE) solve_store<BS, A16>(v.z + o, zv);
+    solve_store<BS, A16>(v.p + o, zv);
+  }
+  const double s0 = solve_block_sum(bb, red[0]), s1 = solve_block_sum(rz, red[1]), s2 = solve_block_sum(rr, red[2]);
+  if (threadIdx.x == 0) {
+    v.part_bb[blockIdx.x] = s0;
+    v.part_rz[blockIdx.x] = s1;
+    v.part_rr[blockIdx.x] = s2;
+  }
+}
+
+// Setup, one wave: the state before the first iteration.  n_bad: partial counts of indefinite blocks in part_pq
+__global__ void __launch_bounds__(64) cg_init_state_kernel(const SolveVectors v, int n_parts, int n_bad, double rtol, double atol)
+{
+  const double bad = solve_wave_sum(v.part_pq, n_bad);
+  const double bb = solve_wave_sum(v.part_bb, n_parts);
+  const double rz = solve_wave_sum(v.part_rz, n_parts);
+  const double rr = solve_wave_sum(v.part_rr, n_parts);
+  if (threadIdx.x != 0) return;
+  SolveState& s = *v.state;
+  const double t = rtol * __builtin_sqrt(bb);
+  const double thresh = t > atol ? t : atol;
+  s.rho[0] = rz;
+  s.rho[1] = 0.0;
+  s.rr = rr;
+  s.bb = bb;
+  s.thresh2 = thresh * thresh;
+  s.iteration = 0;
+  s.flags = bb == 0.0 ? SOLVE_FLAG_ZERO_RHS : 0;
+  s.pad = 0.0;
+  int status = HDD_SOLVE_CONVERGED, done_at = 0x7fffffff;
+  if (bb == 0.0) done_at = 0;                                     // x = 0 (the host clears it)
+  else if (bad > 0.0) status = HDD_SOLVE_BREAKDOWN, done_at = 0;  // a diagonal block is not positive definite
+  else if (solve_finite(rr) && rr <= s.thresh2) done_at = 0;
+  else if (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0)) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
+  s.status = status;
+  s.done_at = done_at;
+  if (v.history) v.history[0] = __builtin_sqrt(rr);
+}
+
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, int k)
+{
+  __shared__ double red[2][4];
+  if (v.state->done_at <= k) return;   // (uniform)
+  const double pq = solve_wave_sum(v.part_pq, v.n_pq);
+  if (!solve_finite(pq) || !(pq > 0.0)) return;   // breakdown: cg_direction_kernel sees the same sum and records it
+  const double alpha = v.state->rho[k & 1] / pq;
+  double rz = 0.0, rr = 0.0;
+  const int64_t n_blk = v.n / BS;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+    const int64_t o = i * BS;
+    double pv[BS], qv[BS], xv[BS], rv[BS], zv[BS];
+    solve_load<BS, A16>(v.p + o, pv);
+    solve_load<BS, A16>(v.q + o, qv);
+    solve_load<BS, A16>(v.x + o, xv);
+    solve_load<BS, A16>(v.r + o, rv);
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+      xv[j] = __builtin_fma(alpha, pv[j], xv[j]);
+      rv[j] = __builtin_fma(-alpha, qv[j], rv[j]);
+    }
+    if constexpr (PRE) solve_precond<BS>(v.dinv + i * solve_packed<BS>(), rv, zv);
+#pragma unroll
+    for (int j = 0; j < BS; ++j) {
+      if constexpr (PRE) rz = __builtin_fma(rv[j], zv[j], rz);
+      rr = __builtin_fma(rv[j], rv[j], rr);
+    }
+    solve_store<BS, A16>(v.x + o, xv);
+    solve_store<BS, A16>(v.r + o, rv);
+    if constexpr (PRE) solve_store<BS, A16>(v.z + o, zv);
+  }
+  const double s0 = solve_block_sum(rz, red[0]), s1 = solve_block_sum(rr, red[1]);
+  if (threadIdx.x == 0) {
+    if constexpr (PRE) v.part_rz[blockIdx.x] = s0;
+    v.part_rr[blockIdx.x] = s1;
+  }
+}
+
+// n_parts: workgroups of the cg_update launch
+template <bool PRE>
+__global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v, int k, int n_parts)
+{
+  SolveState& s = *v.state;
+  if (s.done_at <= k) return;   // (uniform)
+  const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+  const double pq = solve_wave_sum(v.part_pq, v.n_pq);
+  if (!solve_finite(pq) || !(pq > 0.0)) {   // x, r are those of iteration k
+    if (writer) s.status = HDD_SOLVE_BREAKDOWN, s.done_at = k;
+    return;
+  }
+  const double rr = solve_wave_sum(v.part_rr, n_parts);
+  const double rz = PRE ? solve_wave_sum(v.part_rz, n_parts) : rr;
+  const bool converged = solve_finite(rr) && rr <= s.thresh2;
+  const bool broken = !converged && (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0));
+  if (writer) {
+    s.rho[(k + 1) & 1] = rz;
+    s.rr = rr;
+    s.iteration = k + 1;
+    if (v.history) v.history[k + 1] = __builtin_sqrt(rr);
+    if (broken) s.status = HDD_SOLVE_BREAKDOWN;
+    if (converged || broken) s.done_at = k + 1;
+  }
+  if (converged || broken) return;
+  const double beta = rz / s.rho[k & 1];
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < v.n; i += int64_t(gridDim.x) * 256)
+    v.p[i] = __builtin_fma(beta, v.p[i], v.z[i]);
+}
+
+}  // namespace dev
+}  // namespace hdd

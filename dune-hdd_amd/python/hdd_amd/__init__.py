@@ -103,6 +103,18 @@ class BlockRange(C.Structure):
 
 
 MAX_VEC = 8
+PRECOND_NONE, PRECOND_BLOCK_JACOBI = 0, 1
+SOLVE_CONVERGED, SOLVE_MAX_ITER, SOLVE_BREAKDOWN = 0, 1, 2
+SOLVE_X0 = 1
+
+
+class SolveOptions(C.Structure):
+    _fields_ = [("rtol", C.c_double), ("atol", C.c_double), ("max_iter", C.c_int32), ("check_every", C.c_int32),
+                ("precond", C.c_int32), ("block_size", C.c_int32), ("flags", C.c_int32), ("pad", C.c_int32)]
+
+
+class SolveInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("residual", C.c_double), ("rhs_norm", C.c_double)]
 
 
 class ShardInfo(C.Structure):
@@ -225,6 +237,9 @@ def lib():
         "hdd_operator_apply2": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _I32, _VP, _I64, _I32, _VP, _I64,
                                        _VP, _VP]),
         "hdd_last_apply_kernel": (C.c_char_p, []),
+        "hdd_operator_solve_workspace": (_I64, [_I64, _I32]),
+        "hdd_operator_solve": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
+        "hdd_last_solve_kernels": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -238,6 +253,12 @@ def last_apply_kernel():
     """hdd_last_apply_kernel: the kernel this thread's last apply / apply2 launched ("apply_tile_kernel<...>" or
     "apply_csr_kernel<...>")"""
     return lib().hdd_last_apply_kernel().decode()
+
+
+def last_solve_kernels():
+    """hdd_last_solve_kernels: the kernels of one iteration of this thread's last solve, e.g.
+    "apply_tile_kernel<3, 3, 1, dot> + cg_update<3> + cg_direction"""
+    return lib().hdd_last_solve_kernels().decode()
 
 
 def last_tile_kernel():
@@ -915,6 +936,54 @@ def apply2(ctx, dpattern, vals, v, u, theta=None, dmesh=None, block=None, stream
                                      u2.stride(0) if n_u > 1 else max(cols, 1), n_u, work.data_ptr(), work.stride(0),
                                      out.data_ptr(), C.c_void_p(s)), "hdd_operator_apply2")
     return out
+
+
+_PRECONDS = {"none": PRECOND_NONE, "block_jacobi": PRECOND_BLOCK_JACOBI}
+
+
+def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, rtol=1e-8, atol=0.0, max_iter=10000,
+          precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None, grid=None):
+    """hdd_operator_solve: x with (sum_q theta[q] A_q) x = b by (block-)Jacobi preconditioned conjugate gradients on
+    the device -- the apply_inverse of uncached_solve.  Operands as apply's; block: None or a square diagonal block
+    ((ss, ss): the local solve on get_local_operator(ss)).  THE MATRIX MUST BE SYMMETRIC POSITIVE DEFINITE (hdd.h).
+    b: device float64 [rows] (unit stride); x0: the initial guess or None (zero).  block_size 0: nb of dmesh (of the
+    pattern's LocalMesh when dmesh is None; precond="none" without either: 1).  Returns (x, info): info a SolveInfo
+    (status SOLVE_*, iterations, residual, rhs_norm) that also carries .history (device [iterations + 1], ||r_k||) when
+    history=True.  Synchronises the stream at every look (check_every iterations, default 32)."""
+    torch = _torch()
+    vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
+    if precond not in _PRECONDS:
+        raise HddError("solve: precond is one of %s" % sorted(_PRECONDS))
+    if b.dtype != torch.float64 or b.dim() != 1 or b.shape[0] != rows or (rows > 1 and b.stride(0) != 1):
+        raise HddError("solve: b must be float64 [%d] with unit stride" % rows)
+    block_size = int(block_size)
+    if block_size == 0 and dmesh is None:
+        local = getattr(dpattern, "local", None)
+        if local is not None and not getattr(dpattern, "volume", False) and local.nb <= 8:
+            block_size = int(local.nb)
+        elif precond == "none":
+            block_size = 1
+    flags = 0
+    if x0 is None:
+        x = torch.empty(rows, dtype=torch.float64, device=b.device)
+    else:
+        if x0.dtype != torch.float64 or x0.shape != b.shape:
+            raise HddError("solve: x0 must be float64 [%d]" % rows)
+        x = x0.to(b.device, copy=True).contiguous()
+        flags |= SOLVE_X0
+    opt = SolveOptions(float(rtol), float(atol), int(max_iter), int(check_every), _PRECONDS[precond], block_size, flags, 0)
+    n_work = max(int(lib().hdd_operator_solve_workspace(rows, block_size)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
+    hist = torch.zeros(max(int(max_iter), 0) + 1, dtype=torch.float64, device=b.device) if history else None
+    info = SolveInfo()
+    s = stream if stream is not None else torch.cuda.current_stream(b.device).cuda_stream
+    _check(lib().hdd_operator_solve(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
+                                    n, _p(th), None if rng is None else C.addressof(rng), b.data_ptr(), x.data_ptr(),
+                                    C.addressof(opt), work.data_ptr(), n_work,
+                                    None if hist is None else hist.data_ptr(), C.addressof(info), C.c_void_p(s)),
+           "hdd_operator_solve")
+    info.history = None if hist is None else hist[:info.iterations + 1]
+    return x, info
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

@@ -483,6 +483,67 @@ int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* patte
 const char* hdd_last_apply_kernel(void);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* solve -- the apply_inverse of ContainerBasedDefault::uncached_solve (base.hh:327-367) on the      */
+/* theta-fused operator: (block-)Jacobi preconditioned conjugate gradients, on the device between    */
+/* two looks of the host.  Additive to ABI 8.                                                        */
+/* ---------------------------------------------------------------------------------------------- */
+enum { HDD_PRECOND_NONE = 0, HDD_PRECOND_BLOCK_JACOBI = 1 };
+enum { HDD_SOLVE_CONVERGED = 0, HDD_SOLVE_MAX_ITER = 1, HDD_SOLVE_BREAKDOWN = 2 };
+enum { HDD_SOLVE_X0 = 1 };            /* flags: d_x holds the initial guess (default: x0 = 0, d_x need not be set) */
+typedef struct {
+  double rtol, atol;                  /* stop when ||r||_2 <= max(rtol * ||b||_2, atol), r the recurrence residual */
+  int32_t max_iter;
+  int32_t check_every;                /* iterations enqueued between two looks of the host; 0 = default (32) */
+  int32_t precond;                    /* HDD_PRECOND_* */
+  int32_t block_size;                 /* block-Jacobi block: 0 = nb of the mesh (needs mesh); else 1..8 */
+  int32_t flags, pad;
+} hdd_solve_options;
+typedef struct { int32_t status, iterations; double residual, rhs_norm; } hdd_solve_info;
+
+/* doubles of workspace hdd_operator_solve needs for `rows` rows and blocks of block_size (1..8) rows; with
+ * block_size 0 (the mesh's nb, which this function cannot know) enough for every block size.  0 for a negative
+ * rows or a block_size outside 0..8.  The solve checks n_work against the block size it resolves, so block_size 0
+ * on a P1 mesh needs what block_size 3 needs. */
+int64_t hdd_operator_solve_workspace(int64_t rows, int32_t block_size);
+/* Solves (sum_q theta[q] A_q) x = b by preconditioned conjugate gradients.  mesh, pattern, d_vals, n_comp, theta are
+ * hdd_operator_apply's, with the same checks and the same dispatch (the tile kernel where apply takes it, the CSR
+ * kernel otherwise); range is NULL (the whole matrix, which must be square) or a square diagonal range (row_begin ==
+ * col_begin, row_end == col_end): the local solve on a BlockSWIPDG's get_local_operator(ss), in place.  d_b, d_x:
+ * device [rows], ONE right-hand side per call (batched right-hand sides are out of scope).  d_x is overwritten; with
+ * HDD_SOLVE_X0 it is read first as the initial guess.
+ * THE MATRIX MUST BE SYMMETRIC POSITIVE DEFINITE -- BY CALLING THE CALLER ASSERTS THIS; the library cannot check it.
+ * The SWIPDG matrix with the reference's penalties (8 / 14) is positive definite on near-square elements with a
+ * diffusion that is constant per element, but INDEFINITE on stretched elements under a high-contrast diffusion and
+ * for the strongly varying smooth diffusion of OS2014 (tables in DESIGN.md 4.7); HDD_SOLVE_BREAKDOWN is what a
+ * violated assertion may produce (it may also end in MAX_ITER).
+ * Preconditioner: HDD_PRECOND_BLOCK_JACOBI inverts the diagonal blocks of block_size rows (0: nb of the mesh, one
+ * block per element; the bounds of the range, or n_rows, must be multiples of it) once per call into the workspace;
+ * a block with a non-positive pivot gives HDD_SOLVE_BREAKDOWN before the first iteration.
+ * Iteration: three launches (q = A p with p . q in its epilogue; x, r, z and their dot products; the new direction),
+ * no atomics, every sum two-stage in a fixed order: x, iterations and residual are bit-identical from call to call
+ * and do not depend on check_every.  Every launch of an iteration reads a stop word first, which the device sets on
+ * convergence (||r|| <= max(rtol ||b||, atol), r the recurrence residual) or breakdown (p . Ap <= 0, r . z <= 0, a
+ * non-finite scalar): the host enqueues min(check_every, remaining) iterations, then copies 64 bytes of state back
+ * and SYNCHRONISES `stream` -- at every look, and before returning.  info: status HDD_SOLVE_*, the iterations done,
+ * the recurrence ||r||_2 and ||b||_2.  With ||b|| = 0: x = 0, converged, 0 iterations.  On breakdown x is the last
+ * iterate before it.  d_history: NULL or device [max_iter + 1], entry k = ||r_k||_2 for k <= iterations.
+ * Allocates nothing: d_work (n_work >= hdd_operator_solve_workspace doubles, 16-byte aligned for the 16-byte access
+ * paths) holds every vector, the inverse blocks and the state; the context owns the pinned bytes the state is read
+ * back into since its creation.  One stream at a time per context.
+ * Returns HDD_OK for all three statuses; HDD_ERR_INVALID (every argument check precedes the first device call) for a
+ * null ctx / pattern / d_vals / d_b / d_x / opt / d_work / info, what hdd_operator_apply rejects, a range that is
+ * not square and diagonal, max_iter < 0, rtol / atol negative or NaN, check_every < 0, an unknown precond, block_size
+ * outside 0..8, block_size 0 without a mesh of nb <= 8, bounds that are no multiples of the block size, n_work too
+ * small; HDD_ERR_HIP for a HIP failure. */
+int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                       int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_b,
+                       double* d_x, const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history,
+                       hdd_solve_info* info, void* stream);
+/* the kernels of one iteration of this thread's last hdd_operator_solve ("" if none), e.g.
+ * "apply_tile_kernel<3, 3, 1, dot> + cg_update<3> + cg_direction" */
+const char* hdd_last_solve_kernels(void);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */
 /* GPU owns a contiguous range of subdomains and assembles their rows -- A_ss and A_ss,nn are written  */
 /* by the owner of ss (block-swipdg.hh:355-382, coupling 1270-1326, boundary 1136-1179), so there is  */

@@ -66,6 +66,10 @@ struct internal_error : std::runtime_error {
 struct requirements_not_met : std::logic_error {
   using std::logic_error::logic_error;
 };
+// dune-stuff's linear solver exceptions (Stuff::LA::Solver: "linear_solver_failed..."): apply_inverse did not converge
+struct linear_solver_failed : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
 }  // namespace Exceptions
 
 namespace Common {
@@ -607,6 +611,13 @@ class Pattern {
   mutable std::vector<int32_t> h_col_;
 };
 
+// Options of AffinelyDecomposedMatrix::apply_inverse (hdd_solve_options; block_size 0: nb of the system matrix's
+// mesh, 1 without one)
+struct SolverOptions {
+  double rtol = 1e-8, atol = 0.0;
+  int32_t max_iter = 10000, check_every = 0, precond = HDD_PRECOND_BLOCK_JACOBI, block_size = 0;
+};
+
 // AffinelyDecomposedContainer<Matrix>: components on one shared pattern (values on the device)
 class AffinelyDecomposedMatrix {
  public:
@@ -693,6 +704,49 @@ class AffinelyDecomposedMatrix {
                                         std::max<int64_t>(pattern->rows, 1), out.get(), nullptr), "hdd_operator_apply2");
     internal::hip_check(hipDeviceSynchronize(), "apply2");
     return out.download()[0];
+  }
+  using SolverOptions = Discretizations::SolverOptions;
+  // x = A(mu)^-1 b: what uncached_solve does with the container (base.hh:327-367: lincomb, then apply_inverse), by
+  // hdd_operator_solve -- A(mu) is never written, theta is fused into the iteration's applies.  A(mu) must be
+  // symmetric positive definite (hdd.h).  d_b, d_x: device [rows of the -- restricted -- operator]; x0: d_x holds
+  // the initial guess.  Synchronises `stream`.  Throws linear_solver_failed unless the solve converged.
+  hdd_solve_info apply_inverse(const double* d_b, double* d_x, double mu = 0.0, const SolverOptions& options = SolverOptions(),
+                               const hdd_block_range* range = nullptr, bool x0 = false, void* stream = nullptr) const
+  {
+    std::vector<const double*> v;
+    std::vector<double> theta;
+    operands(mu, v, theta);
+    const hdd_csr pat = pattern->csr();
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    hdd_solve_options opt{options.rtol, options.atol, options.max_iter, options.check_every, options.precond,
+                          options.block_size, x0 ? HDD_SOLVE_X0 : 0, 0};
+    if (opt.block_size == 0 && !tile_nbrs) opt.block_size = 1;
+    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_workspace(rows, opt.block_size), 1);
+    internal::DeviceArray<double> work{size_t(n_work)};
+    hdd_solve_info info{};
+    internal::check(hdd_operator_solve(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
+                                       theta.data(), range, d_b, d_x, &opt, work.get(), n_work, nullptr, &info, stream),
+                    "hdd_operator_solve");
+    if (info.status != HDD_SOLVE_CONVERGED)
+      throw Stuff::Exceptions::linear_solver_failed(
+          std::string("apply_inverse: linear solver failed (") +
+          (info.status == HDD_SOLVE_MAX_ITER ? "max_iter reached" : "breakdown: the matrix is not positive definite?") +
+          ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) +
+          " iterations, residual " + std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm));
+    return info;
+  }
+  std::vector<double> apply_inverse(const std::vector<double>& b, double mu = 0.0, const SolverOptions& options = SolverOptions(),
+                                    const hdd_block_range* range = nullptr, hdd_solve_info* info = nullptr) const
+  {
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    if (int64_t(b.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
+    internal::DeviceArray<double> db{size_t(std::max<int64_t>(rows, 1))}, dx{size_t(std::max<int64_t>(rows, 1))};
+    if (rows) internal::hip_check(hipMemcpy(db.get(), b.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_inverse");
+    const hdd_solve_info i = apply_inverse(db.get(), dx.get(), mu, options, range);
+    if (info) *info = i;
+    auto x = dx.download();
+    x.resize(size_t(rows));
+    return x;
   }
   // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
   // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
@@ -994,6 +1048,23 @@ class SWIPDG {
     return rhs_;
   }
   const AffinelyDecomposedVector& get_rhs() const { return rhs(); }
+
+  // uncached_solve (base.hh:327-367): the right-hand side's affine part and components combined with their theta(mu)
+  // on the host, the matrix's theta fused into the device solve (AffinelyDecomposedMatrix::apply_inverse)
+  std::vector<double> solve(double mu = 0.0,
+                            const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                            hdd_solve_info* info = nullptr) const
+  {
+    const auto& b = rhs();
+    std::vector<double> bmu(size_t(b.size), 0.0);
+    if (b.affine) bmu = b.affine_part();
+    for (int q = 0; q < b.num_components(); ++q) {
+      const double th = b.coefficient(q).evaluate(mu);
+      const auto c = b.component(q);
+      for (size_t i = 0; i < bmu.size(); ++i) bmu[i] += th * c[i];
+    }
+    return system_matrix().apply_inverse(bmu, mu, options, nullptr, info);
+  }
 
   // base.hh:272-291: only the products requested in the ctor (only_these_products, swipdg.hh:496-508)
   std::vector<std::string> available_products() const
@@ -1476,6 +1547,21 @@ class BlockSWIPDG : public SWIPDG {
                                                   std::to_string(ss) + " (call neighbouring_subdomains(" +
                                                   std::to_string(ss) + ") to find out)!");
     return apply_block(ss, nn, x, mu);
+  }
+
+  // The local solve get_local_operator(ss)^-1 b WITHOUT extracting the operator: the diagonal block of ss of the
+  // global matrix through a block range (hdd_operator_solve; the diagonal block of an SPD matrix is SPD).  b and the
+  // result in ss's local numbering.
+  std::vector<double> solve_local(int ss, const std::vector<double>& b, double mu = 0.0,
+                                  const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                  hdd_solve_info* info = nullptr) const
+  {
+    range_check(ss);
+    int64_t a, e;
+    internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &e), "range");
+    const int64_t nb = info_.nb;
+    const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
+    return system_matrix().apply_inverse(b, mu, options, &rng, info);
   }
 
   // block-swipdg.hh:678-685: the local vector of ss (local discretization rhs + boundary contributions) =
