@@ -39,8 +39,8 @@ extern "C" int hdd_ctx_create(int hip_device, hdd_ctx** out)
     delete c;
     return hip_fail(e, "hdd_ctx_create: hipMalloc");
   }
-  // hdd_operator_solve reads its state back at every look and may not allocate either
-  e = hipHostMalloc(reinterpret_cast<void**>(&c->solve_state_h), 64, hipHostMallocDefault);
+  // hdd_operator_solve / _solve_batched read their states back at every look and may not allocate either
+  e = hipHostMalloc(reinterpret_cast<void**>(&c->solve_state_h), hdd_ctx::SOLVE_STATE_BYTES, hipHostMallocDefault);
   if (e != hipSuccess) {
     c->solve_state_h = nullptr;
     delete c;

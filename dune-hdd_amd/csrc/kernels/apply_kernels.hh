@@ -17,10 +17,13 @@
 // apply_csr_kernel -- plain CSR on row_ptr / col for everything else; a group of G lanes per row (8 for the short
 //   rows of P1 / Q1 / volume patterns, a wave for the hexahedral Q_p rows), shuffle reduction in a fixed order.
 // apply2_partial_kernel / apply2_final_kernel -- out[i][j] = v_i . w_j in two deterministic stages.
-// DOT variants (NV = 1, a square diagonal range: x and y share their numbering) also leave x . y behind, for the
+// DOT variants (a square diagonal range: x and y share their numbering) also leave x_v . y_v behind, for the
 //   conjugate gradient iteration: every lane adds x_r y_r of its own rows over its tiles / rows in order, the
-//   workgroup reduces once at the end (shuffle tree, then the waves in order) and writes partial[blockIdx].  The
-//   instantiations without DOT are unchanged by it (same registers).
+//   workgroup reduces once at the end (shuffle tree, then the waves in order) and writes
+//   partial[v * gridDim.x + blockIdx.x].  Every vector has its own chain and its own tree, those of the NV = 1
+//   instantiation: with the same grid, vector v's partial sums are bit for bit those of a one-vector launch on it
+//   (the batched solve rests on this).  The instantiations without DOT are unchanged by it (same registers,
+//   DESIGN.md 4.6).
 // No atomics anywhere: results are bit-identical from call to call.
 #pragma once
 #include <cstdint>
@@ -51,8 +54,9 @@ struct ApplyArgs {
   int64_t ldx;
   double* y;                           // y[v * ldy + row - row_begin]
   int64_t ldy;
-  // DOT variants only (hdd_operator_solve, solve_kernels.hh): partial[blockIdx] = this workgroup's share of x . y, and
-  // the iteration's stop word -- the launch returns at once when *done_at <= iteration
+  // DOT variants only (hdd_operator_solve[_batched], solve_kernels.hh): partial[v * gridDim + blockIdx] = this
+  // workgroup's share of x_v . y_v, and the iteration's stop word -- the launch returns at once when
+  // *done_at <= iteration
   double* partial;
   const int32_t* done_at;
   int32_t iteration;
@@ -91,12 +95,11 @@ __device__ __forceinline__ int apply_swz(int p) { return p ^ (((p >> 5) & 15) <<
 template <int NB, int NF, int NV, bool DOT = false>
 __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
 {
-  static_assert(!DOT || NV == 1, "the dot product is that of one vector");
   using I = ApplyImage<NB, NF>;
   constexpr int CH = I::CHUNKS, U = I::U;
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int lane = threadIdx.x;
-  double dot = 0.0;   // DOT: this lane's x . y over its elements, in tile order
+  [[maybe_unused]] double dot[NV] = {};   // DOT: this lane's x_v . y_v over its elements, in tile order
   if constexpr (DOT)
     if (*a.done_at <= a.iteration) return;   // (wave-uniform)
   const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
@@ -172,7 +175,7 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       }
     const int rl = NB * (nint + 1);   // row length
     double acc[NV][NB];
-    [[maybe_unused]] double xown[NB] = {};
+    [[maybe_unused]] double xown[NV][NB] = {};
 #pragma unroll
     for (int v = 0; v < NV; ++v)
 #pragma unroll
@@ -189,7 +192,9 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       if constexpr (DOT)   // the element's own block is one of the gathered ones: these are its rows of x
         if (id[b] == int(e))
 #pragma unroll
-          for (int j = 0; j < NB; ++j) xown[j] = xv[0][j];
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) xown[v][j] = xv[v][j];
 #pragma unroll
       for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -207,12 +212,17 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
         for (int i = 0; i < NB; ++i) yo[v * a.ldy + i] = acc[v][i];
     if constexpr (DOT)
 #pragma unroll
-      for (int i = 0; i < NB; ++i) dot = __builtin_fma(xown[i], acc[0][i], dot);
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) dot[v] = __builtin_fma(xown[v][i], acc[v][i], dot[v]);
   }
   if constexpr (DOT) {   // every lane is back here, whatever its tiles were
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) dot += __shfl_xor(dot, d, 64);
-    if (lane == 0) a.partial[blockIdx.x] = dot;
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      if (lane == 0 && v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = dot[v];
+    }
   }
 }
 
@@ -220,8 +230,7 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
 template <int G, int NV, bool DOT = false>
 __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
 {
-  static_assert(!DOT || NV == 1, "the dot product is that of one vector");
-  double dot = 0.0;   // DOT: the group leaders' x_r y_r over their rows, in row order
+  [[maybe_unused]] double dot[NV] = {};   // DOT: the group leaders' x_r y_r over their rows, in row order
   if constexpr (DOT)
     if (*a.done_at <= a.iteration) return;   // (uniform)
   const int gl = threadIdx.x % G;
@@ -253,15 +262,24 @@ __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
       for (int v = 0; v < NV; ++v)
         if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
     if constexpr (DOT)
-      if (gl == 0) dot = __builtin_fma(a.x[rr], acc[0], dot);   // square diagonal range: row rr is column rr
+      if (gl == 0)   // square diagonal range: row rr is column rr
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+          if (v < a.nv) dot[v] = __builtin_fma(a.x[v * a.ldx + rr], acc[v], dot[v]);
   }
   if constexpr (DOT) {
-    __shared__ double red[4];
+    __shared__ double red[NV][4];
 #pragma unroll
-    for (int d = 32; d > 0; d >>= 1) dot += __shfl_xor(dot, d, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = dot;
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      if ((threadIdx.x & 63) == 0) red[v][threadIdx.x >> 6] = dot[v];
+    }
     __syncthreads();
-    if (threadIdx.x == 0) a.partial[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
   }
 }
 

@@ -77,7 +77,10 @@ struct hdd_ctx {
   hipEvent_t rhs_evt = nullptr;       //   a call on another stream waits for it (the list is shared state)
   bool rhs_used = false;
   double* apply2_ws = nullptr;   // hdd_operator_apply2's partial sums, allocated with the context (the call allocates nothing)
-  double* solve_state_h = nullptr;   // hdd_operator_solve: 64 pinned host bytes its device state is read back into
+  // hdd_operator_solve[_batched]: pinned host bytes the device state is read back into -- one 64-byte state per
+  // column (HDD_MAX_VEC of them) and 64 bytes of group stop words behind them
+  static constexpr size_t SOLVE_STATE_BYTES = (HDD_MAX_VEC + 1) * 64;
+  double* solve_state_h = nullptr;
 
   // the scratch buffers release themselves; what is left are the plain members
   ~hdd_ctx()

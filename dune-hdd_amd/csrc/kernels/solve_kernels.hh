@@ -17,6 +17,7 @@
 // Every sum is two-stage in a fixed order: bit-identical from call to call, and independent of check_every.
 // The build has -ffinite-math-only: non-finite scalars are recognised by their bits, behind an optimisation barrier
 // (solve_finite).
+// Several right-hand sides per call (hdd_operator_solve_batched): the section at the end of this file.
 #pragma once
 #include <cstdint>
 
@@ -52,6 +53,15 @@ __device__ __forceinline__ bool solve_finite(double v)
   uint64_t u = uint64_t(__double_as_longlong(v));
   asm volatile("" : "+v"(u));   // opaque: under -ffinite-math-only the test on the bits would be folded to true
   return ((u >> 52) & 0x7ff) != 0x7ff;
+}
+
+// b . b == 0 by its bits (either sign of zero): under -ffinite-math-only `bb == 0.0` may hold for a NaN, and a
+// right-hand side with a NaN is a breakdown, not the zero right-hand side
+__device__ __forceinline__ bool solve_is_zero(double v)
+{
+  uint64_t u = uint64_t(__double_as_longlong(v));
+  asm volatile("" : "+v"(u));
+  return (u << 1) == 0;
 }
 
 // sum of part[0, n) by one wave, lane l the entries l, l + 64, ... in order, then a butterfly: every lane of every
@@ -290,10 +300,11 @@ __global__ void __launch_bounds__(64) cg_init_state_kernel(const SolveVectors v,
   s.bb = bb;
   s.thresh2 = thresh * thresh;
   s.iteration = 0;
-  s.flags = bb == 0.0 ? SOLVE_FLAG_ZERO_RHS : 0;
+  const bool zero_rhs = solve_is_zero(bb);
+  s.flags = zero_rhs ? SOLVE_FLAG_ZERO_RHS : 0;
   s.pad = 0.0;
   int status = HDD_SOLVE_CONVERGED, done_at = 0x7fffffff;
-  if (bb == 0.0) done_at = 0;                                     // x = 0 (the host clears it)
+  if (zero_rhs) done_at = 0;                                      // x = 0 (the host clears it)
   else if (bad > 0.0) status = HDD_SOLVE_BREAKDOWN, done_at = 0;  // a diagonal block is not positive definite
   else if (solve_finite(rr) && rr <= s.thresh2) done_at = 0;
   else if (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0)) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
@@ -369,6 +380,215 @@ __global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v,
   const double beta = rz / s.rho[k & 1];
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < v.n; i += int64_t(gridDim.x) * 256)
     v.p[i] = __builtin_fma(beta, v.p[i], v.z[i]);
+}
+
+// ---- several right-hand sides per call (hdd_operator_solve_batched) ----------------------------------------------
+// The columns run in groups of up to APPLY_NV, the apply's pass width: one iteration of a group is the same three
+// launches with NV = APPLY_NV, the value stream and the inverse blocks read once for the group.  Every column keeps
+// the arithmetic of the single solve -- its own FMA chains, its own partial sums [column][workgroup] on the single
+// solve's grids, its own SolveState -- so column j ends with the bits hdd_operator_solve gives for (b_j, x0_j).
+//
+// Two kinds of stop words.  state[c].done_at is column c's (as above): a column that is done is frozen, no later
+// launch touches its x, r, z or p (the apply still writes its q, which nobody reads).  *stop is the group's: the
+// iteration at which its last live column ended (INT32_MAX while one is live); a launch of iteration k returns at
+// once when *stop <= k.  Only cg_direction_batched_kernel writes either word during the iteration, one lane of
+// workgroup 0, while the other workgroups of the same launch k read them -- and decide the same for the old and
+// for the new value:
+//   done_at[c]  old INT32_MAX, new k + 1 (converged / r . z breakdown): `<= k` is false both ways.  New k (p . q
+//               breakdown): a reader of the old value forms the same p . q from the same partial sums and skips the
+//               column as well.
+//   *stop       old INT32_MAX, new the largest done_at of the group, which is k + 1 (false both ways) unless every
+//               column that was still live broke down on its p . q in this launch (new value <= k): a reader of the
+//               old value then finds every column done or broken and touches nothing either.
+// The launches before (apply, update of iteration k) and after (iteration k + 1) are ordered by the stream.
+
+struct SolveBatch {
+  SolveState* state;                    // [nv], the group's columns
+  int32_t* stop;                        // the group's stop word
+  double* x;                            // x[c * ldx + row], the caller's
+  int64_t ldx;
+  double *p, *q, *r, *z;                // [c * ldw + row]; z == r without a preconditioner
+  int64_t ldw;
+  const double* dinv;                   // shared by all columns
+  double *part_pq, *part_rz, *part_rr;  // [c * n_pq + workgroup], [c * n_parts + workgroup]
+  int64_t n;                            // rows
+  int32_t n_pq, nv;
+  double* history;                      // nullable, history[c * ldh + k]
+  int64_t ldh;
+};
+
+// z = D^-1 r from the packed inverse block already in registers: the arithmetic of solve_precond
+template <int BS>
+__device__ __forceinline__ void solve_precond_regs(const double (&m)[BS * (BS + 1) / 2], const double (&r)[BS], double (&z)[BS])
+{
+#pragma unroll
+  for (int i = 0; i < BS; ++i) {
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < BS; ++j) s = __builtin_fma(i >= j ? m[i * (i + 1) / 2 + j] : m[j * (j + 1) / 2 + i], r[j], s);
+    z[i] = s;
+  }
+}
+
+// Setup, one wave: the states of all n_rhs columns before the first iteration (cg_init_state_kernel's sums and
+// decisions per column; the partial sums are [column][n_parts]), then the stop words of the groups of APPLY_NV
+__global__ void __launch_bounds__(64) cg_init_state_batched_kernel(SolveState* state, int32_t* stop, int n_rhs, const double* part_bad,
+                                                                   int n_bad, const double* part_bb, const double* part_rz,
+                                                                   const double* part_rr, int n_parts, double rtol, double atol,
+                                                                   double* history, int64_t ldh)
+{
+  const double bad = solve_wave_sum(part_bad, n_bad);
+  unsigned live = 0;   // (lane 0) bit c: column c iterates
+  for (int c = 0; c < n_rhs; ++c) {
+    const double bb = solve_wave_sum(part_bb + int64_t(c) * n_parts, n_parts);
+    const double rz = solve_wave_sum(part_rz + int64_t(c) * n_parts, n_parts);
+    const double rr = solve_wave_sum(part_rr + int64_t(c) * n_parts, n_parts);
+    if (threadIdx.x != 0) continue;
+    SolveState& s = state[c];
+    const double t = rtol * __builtin_sqrt(bb);
+    const double thresh = t > atol ? t : atol;
+    s.rho[0] = rz;
+    s.rho[1] = 0.0;
+    s.rr = rr;
+    s.bb = bb;
+    s.thresh2 = thresh * thresh;
+    s.iteration = 0;
+    const bool zero_rhs = solve_is_zero(bb);
+    s.flags = zero_rhs ? SOLVE_FLAG_ZERO_RHS : 0;
+    s.pad = 0.0;
+    int status = HDD_SOLVE_CONVERGED, done_at = 0x7fffffff;
+    if (zero_rhs) done_at = 0;
+    else if (bad > 0.0) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
+    else if (solve_finite(rr) && rr <= s.thresh2) done_at = 0;
+    else if (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0)) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
+    s.status = status;
+    s.done_at = done_at;
+    if (done_at != 0) live |= 1u << c;
+    if (history) history[int64_t(c) * ldh] = __builtin_sqrt(rr);
+  }
+  if (threadIdx.x != 0) return;
+  for (int g = 0; g * APPLY_NV < n_rhs; ++g) stop[g] = ((live >> (g * APPLY_NV)) & ((1u << APPLY_NV) - 1)) ? 0x7fffffff : 0;
+}
+
+// cg_update_kernel for a group: the grid and the lane -> block mapping are the single solve's; the lane loads its
+// packed inverse block once and uses it for every live column.  The per-column accumulators are indexed at compile
+// time (unrolled over NV, guarded), so they stay in registers.
+template <int BS, bool PRE, bool A16, int NV>
+__global__ void __launch_bounds__(256) cg_update_batched_kernel(const SolveBatch v, int k)
+{
+  __shared__ double red[NV][2][4];
+  if (*v.stop <= k) return;   // (uniform)
+  bool live[NV];
+  double alpha[NV], rz[NV], rr[NV];
+  bool any = false;
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    live[c] = false;
+    alpha[c] = rz[c] = rr[c] = 0.0;
+    if (c < v.nv && v.state[c].done_at > k) {   // (uniform)
+      const double pq = solve_wave_sum(v.part_pq + int64_t(c) * v.n_pq, v.n_pq);
+      // a breakdown: cg_direction_batched_kernel sees the same sum and records it
+      if (solve_finite(pq) && pq > 0.0) {
+        live[c] = true;
+        alpha[c] = v.state[c].rho[k & 1] / pq;
+      }
+    }
+    any = any || live[c];
+  }
+  if (!any) return;
+  const int64_t n_blk = v.n / BS;
+  const int64_t n_parts = gridDim.x;
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+    const int64_t o = i * BS;
+    [[maybe_unused]] double m[solve_packed<BS>()];
+    if constexpr (PRE) {
+#pragma unroll
+      for (int j = 0; j < solve_packed<BS>(); ++j) m[j] = v.dinv[i * solve_packed<BS>() + j];
+    }
+#pragma unroll
+    for (int c = 0; c < NV; ++c) {
+      if (!live[c]) continue;
+      const int64_t ow = c * v.ldw + o, ox = c * v.ldx + o;
+      double pv[BS], qv[BS], xv[BS], rv[BS], zv[BS];
+      solve_load<BS, A16>(v.p + ow, pv);
+      solve_load<BS, A16>(v.q + ow, qv);
+      solve_load<BS, A16>(v.x + ox, xv);
+      solve_load<BS, A16>(v.r + ow, rv);
+#pragma unroll
+      for (int j = 0; j < BS; ++j) {
+        xv[j] = __builtin_fma(alpha[c], pv[j], xv[j]);
+        rv[j] = __builtin_fma(-alpha[c], qv[j], rv[j]);
+      }
+      if constexpr (PRE) solve_precond_regs<BS>(m, rv, zv);
+#pragma unroll
+      for (int j = 0; j < BS; ++j) {
+        if constexpr (PRE) rz[c] = __builtin_fma(rv[j], zv[j], rz[c]);
+        rr[c] = __builtin_fma(rv[j], rv[j], rr[c]);
+      }
+      solve_store<BS, A16>(v.x + ox, xv);
+      solve_store<BS, A16>(v.r + ow, rv);
+      if constexpr (PRE) solve_store<BS, A16>(v.z + ow, zv);
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    if (!live[c]) continue;   // (uniform)
+    const double s0 = solve_block_sum(rz[c], red[c][0]), s1 = solve_block_sum(rr[c], red[c][1]);
+    if (threadIdx.x == 0) {
+      if constexpr (PRE) v.part_rz[c * n_parts + blockIdx.x] = s0;
+      v.part_rr[c * n_parts + blockIdx.x] = s1;
+    }
+  }
+}
+
+// cg_direction_kernel for a group; n_parts: workgroups of the cg_update launch.  The race argument is at the top
+// of this section.
+template <bool PRE, int NV>
+__global__ void __launch_bounds__(256) cg_direction_batched_kernel(const SolveBatch v, int k, int n_parts)
+{
+  if (*v.stop <= k) return;   // (uniform)
+  const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
+  int ended = 0;       // (writer) the largest done_at of the group's columns
+  bool any = false;    // a column goes on
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    if (c >= v.nv) continue;
+    SolveState& s = v.state[c];
+    const int d = s.done_at;
+    if (d <= k) {   // frozen
+      ended = ended > d ? ended : d;
+      continue;
+    }
+    const double pq = solve_wave_sum(v.part_pq + int64_t(c) * v.n_pq, v.n_pq);
+    if (!solve_finite(pq) || !(pq > 0.0)) {   // x, r are those of iteration k
+      if (writer) s.status = HDD_SOLVE_BREAKDOWN, s.done_at = k;
+      ended = ended > k ? ended : k;
+      continue;
+    }
+    const double rr = solve_wave_sum(v.part_rr + int64_t(c) * n_parts, n_parts);
+    const double rz = PRE ? solve_wave_sum(v.part_rz + int64_t(c) * n_parts, n_parts) : rr;
+    const bool converged = solve_finite(rr) && rr <= s.thresh2;
+    const bool broken = !converged && (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0));
+    if (writer) {
+      s.rho[(k + 1) & 1] = rz;
+      s.rr = rr;
+      s.iteration = k + 1;
+      if (v.history) v.history[c * v.ldh + k + 1] = __builtin_sqrt(rr);
+      if (broken) s.status = HDD_SOLVE_BREAKDOWN;
+      if (converged || broken) s.done_at = k + 1;
+    }
+    if (converged || broken) {
+      ended = k + 1;
+      continue;
+    }
+    any = true;
+    const double beta = rz / s.rho[k & 1];
+    double* p = v.p + c * v.ldw;
+    const double* z = v.z + c * v.ldw;
+    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < v.n; i += int64_t(gridDim.x) * 256)
+      p[i] = __builtin_fma(beta, p[i], z[i]);
+  }
+  if (writer && !any) *v.stop = ended;
 }
 
 }  // namespace dev

@@ -240,6 +240,9 @@ def lib():
         "hdd_operator_solve_workspace": (_I64, [_I64, _I32]),
         "hdd_operator_solve": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
         "hdd_last_solve_kernels": (C.c_char_p, []),
+        "hdd_operator_solve_batched_workspace": (_I64, [_I64, _I32, _I32]),
+        "hdd_operator_solve_batched": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _VP, _I64,
+                                              _VP, _I64, _VP, _VP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -984,6 +987,62 @@ def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, r
            "hdd_operator_solve")
     info.history = None if hist is None else hist[:info.iterations + 1]
     return x, info
+
+
+def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0=None, rtol=1e-8, atol=0.0,
+                  max_iter=10000, precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None,
+                  grid=None):
+    """hdd_operator_solve_batched: solve()'s system for the n_rhs (1..MAX_VEC) rows of B at once -- pyMOR's
+    apply_inverse on a VectorArray.  B: device float64 [n_rhs, rows] with unit inner stride (its row stride is ldb);
+    X0: per-column initial guesses of B's shape, or None.  Every other argument is solve()'s and holds for all
+    columns.  Returns (X, infos): X [n_rhs, rows], infos a list of SolveInfo (each with .history when history=True).
+    Column j is bit for bit what solve() gives for (B[j], X0[j]); the value arrays and the inverse blocks are read
+    once per group of four columns and iteration."""
+    torch = _torch()
+    vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
+    if precond not in _PRECONDS:
+        raise HddError("solve_batched: precond is one of %s" % sorted(_PRECONDS))
+    if B.dtype != torch.float64 or B.dim() != 2 or B.shape[1] != rows or (rows > 1 and B.stride(1) != 1):
+        raise HddError("solve_batched: B must be float64 [n_rhs, %d] with unit inner stride" % rows)
+    n_rhs = int(B.shape[0])
+    if not 1 <= n_rhs <= MAX_VEC:
+        raise HddError("solve_batched: n_rhs outside 1..%d" % MAX_VEC)
+    ldb = int(B.stride(0)) if n_rhs > 1 else max(rows, 1)
+    if n_rhs > 1 and ldb < rows:
+        raise HddError("solve_batched: the rows of B overlap")
+    block_size = int(block_size)
+    if block_size == 0 and dmesh is None:
+        local = getattr(dpattern, "local", None)
+        if local is not None and not getattr(dpattern, "volume", False) and local.nb <= 8:
+            block_size = int(local.nb)
+        elif precond == "none":
+            block_size = 1
+    flags = 0
+    if X0 is None:
+        X = torch.empty((n_rhs, rows), dtype=torch.float64, device=B.device)
+    else:
+        if X0.dtype != torch.float64 or X0.shape != B.shape:
+            raise HddError("solve_batched: X0 must be float64 [%d, %d]" % (n_rhs, rows))
+        X = X0.to(B.device, copy=True).contiguous()
+        flags |= SOLVE_X0
+    opt = SolveOptions(float(rtol), float(atol), int(max_iter), int(check_every), _PRECONDS[precond], block_size, flags, 0)
+    n_work = max(int(lib().hdd_operator_solve_batched_workspace(rows, block_size, n_rhs)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=B.device)
+    ldh = max(int(max_iter), 0) + 1
+    hist = torch.zeros((n_rhs, ldh), dtype=torch.float64, device=B.device) if history else None
+    infos = (SolveInfo * n_rhs)()
+    s = stream if stream is not None else torch.cuda.current_stream(B.device).cuda_stream
+    _check(lib().hdd_operator_solve_batched(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t),
+                                            ptrs, n, _p(th), None if rng is None else C.addressof(rng), B.data_ptr(), ldb,
+                                            X.data_ptr(), max(rows, 1), n_rhs, C.addressof(opt), work.data_ptr(), n_work,
+                                            None if hist is None else hist.data_ptr(), ldh, C.addressof(infos),
+                                            C.c_void_p(s)), "hdd_operator_solve_batched")
+    out = []
+    for j in range(n_rhs):
+        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
+        i.history = None if hist is None else hist[j, :i.iterations + 1]
+        out.append(i)
+    return X, out
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

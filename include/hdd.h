@@ -509,7 +509,7 @@ int64_t hdd_operator_solve_workspace(int64_t rows, int32_t block_size);
  * hdd_operator_apply's, with the same checks and the same dispatch (the tile kernel where apply takes it, the CSR
  * kernel otherwise); range is NULL (the whole matrix, which must be square) or a square diagonal range (row_begin ==
  * col_begin, row_end == col_end): the local solve on a BlockSWIPDG's get_local_operator(ss), in place.  d_b, d_x:
- * device [rows], ONE right-hand side per call (batched right-hand sides are out of scope).  d_x is overwritten; with
+ * device [rows], one right-hand side per call (several: hdd_operator_solve_batched below).  d_x is overwritten; with
  * HDD_SOLVE_X0 it is read first as the initial guess.
  * THE MATRIX MUST BE SYMMETRIC POSITIVE DEFINITE -- BY CALLING THE CALLER ASSERTS THIS; the library cannot check it.
  * The SWIPDG matrix with the reference's penalties (8 / 14) is positive definite on near-square elements with a
@@ -525,7 +525,8 @@ int64_t hdd_operator_solve_workspace(int64_t rows, int32_t block_size);
  * convergence (||r|| <= max(rtol ||b||, atol), r the recurrence residual) or breakdown (p . Ap <= 0, r . z <= 0, a
  * non-finite scalar): the host enqueues min(check_every, remaining) iterations, then copies 64 bytes of state back
  * and SYNCHRONISES `stream` -- at every look, and before returning.  info: status HDD_SOLVE_*, the iterations done,
- * the recurrence ||r||_2 and ||b||_2.  With ||b|| = 0: x = 0, converged, 0 iterations.  On breakdown x is the last
+ * the recurrence ||r||_2 and ||b||_2.  With ||b|| = 0: x = 0, converged, 0 iterations (a right-hand side that holds a
+ * NaN is not that: it is a breakdown before the first iteration).  On breakdown x is the last
  * iterate before it.  d_history: NULL or device [max_iter + 1], entry k = ||r_k||_2 for k <= iterations.
  * Allocates nothing: d_work (n_work >= hdd_operator_solve_workspace doubles, 16-byte aligned for the 16-byte access
  * paths) holds every vector, the inverse blocks and the state; the context owns the pinned bytes the state is read
@@ -542,6 +543,40 @@ int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* patter
 /* the kernels of one iteration of this thread's last hdd_operator_solve ("" if none), e.g.
  * "apply_tile_kernel<3, 3, 1, dot> + cg_update<3> + cg_direction" */
 const char* hdd_last_solve_kernels(void);
+
+/* Several right-hand sides against one matrix per call: pyMOR's apply_inverse on a VectorArray (the Riesz
+ * representatives product^-1 R of a reductor), the local corrections of LRBMS on one get_local_operator(ss).
+ * Additive to ABI 8.
+ * doubles of workspace hdd_operator_solve_batched needs: the vectors and partial sums per right-hand side, the
+ * inverse blocks once.  block_size as in hdd_operator_solve_workspace; 0 for a negative rows, a block_size outside
+ * 0..8 or n_rhs outside 1..HDD_MAX_VEC. */
+int64_t hdd_operator_solve_batched_workspace(int64_t rows, int32_t block_size, int32_t n_rhs);
+/* hdd_operator_solve for n_rhs (1..HDD_MAX_VEC) right-hand sides: d_b is [n_rhs][ldb], d_x [n_rhs][ldx] (ldb, ldx >=
+ * rows; d_x must not overlap d_b), d_history NULL or [n_rhs][ldh] with ldh >= max_iter + 1, info host [n_rhs].  The
+ * operator arguments, the range rule, the dispatch and the options are hdd_operator_solve's; one hdd_solve_options
+ * holds for every column, and with HDD_SOLVE_X0 every column of d_x is read as that column's initial guess.
+ * Column j ends with exactly the x, iterations, residual, rhs_norm, status and history that hdd_operator_solve gives
+ * for (b_j, x0_j) with the same options -- the doubles bit for bit, whatever the other columns hold and whatever
+ * check_every is.  A column that is done (converged, broken down, zero right-hand side) is frozen: later iterations
+ * do not touch its x.  A NaN or a breakdown (p . Ap <= 0) stays in its own column; a diagonal block that is not
+ * positive definite breaks every column down before the first iteration; a zero column gives x_j = 0, converged, 0
+ * iterations.  Returns HDD_OK for every mix of per-column statuses.
+ * The columns run in groups of four (the multi-vector pass of hdd_operator_apply): per group and iteration the same
+ * three launches as hdd_operator_solve, which read the value arrays and the inverse blocks once for the group.  Each
+ * column keeps its own sums on the single solve's grids, its own 64-byte state and stop word; a group has a stop
+ * word of its own (the iteration at which its last live column ended).  At every look the host copies all states
+ * back in one copy and SYNCHRONISES `stream`; it stops when every column is done or max_iter is reached.
+ * Allocates nothing, no atomics, one stream at a time per context.  HDD_ERR_INVALID (every argument check precedes
+ * the first device call) for what hdd_operator_solve rejects, n_rhs outside 1..HDD_MAX_VEC, ldb or ldx < rows, a
+ * history with ldh < max_iter + 1, n_work below hdd_operator_solve_batched_workspace, a null info.
+ * hdd_last_solve_kernels() afterwards names the batched kernels with the vector count of their instantiation (4, not
+ * n_rhs): "apply_tile_kernel<3, 3, 4, dot> + cg_update<3, 4> + cg_direction<4>" (without a preconditioner
+ * "cg_update<3, none, 4>"). */
+int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                               int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_b,
+                               int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs, const hdd_solve_options* opt,
+                               double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
+                               void* stream);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */

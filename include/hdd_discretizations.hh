@@ -748,6 +748,65 @@ class AffinelyDecomposedMatrix {
     x.resize(size_t(rows));
     return x;
   }
+  // X = A(mu)^-1 B for n_rhs (1..HDD_MAX_VEC) right-hand sides at once (hdd_operator_solve_batched: pyMOR's
+  // apply_inverse on a VectorArray): d_b [n_rhs][ldb], d_x [n_rhs][ldx] device arrays.  Column j is bit for bit what
+  // the single apply_inverse gives for it; the value arrays are read once per group of four columns and iteration.
+  // Throws linear_solver_failed naming the first column that did not converge.
+  std::vector<hdd_solve_info> apply_inverse(const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs, double mu = 0.0,
+                                            const SolverOptions& options = SolverOptions(), const hdd_block_range* range = nullptr,
+                                            bool x0 = false, void* stream = nullptr) const
+  {
+    if (n_rhs < 1 || n_rhs > HDD_MAX_VEC) throw Stuff::Exceptions::wrong_input_given("apply_inverse: n_rhs outside 1..HDD_MAX_VEC");
+    std::vector<const double*> v;
+    std::vector<double> theta;
+    operands(mu, v, theta);
+    const hdd_csr pat = pattern->csr();
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    hdd_solve_options opt{options.rtol, options.atol, options.max_iter, options.check_every, options.precond,
+                          options.block_size, x0 ? HDD_SOLVE_X0 : 0, 0};
+    if (opt.block_size == 0 && !tile_nbrs) opt.block_size = 1;
+    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_batched_workspace(rows, opt.block_size, n_rhs), 1);
+    internal::DeviceArray<double> work{size_t(n_work)};
+    std::vector<hdd_solve_info> infos(size_t(n_rhs), hdd_solve_info{});
+    internal::check(hdd_operator_solve_batched(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
+                                               theta.data(), range, d_b, ldb, d_x, ldx, n_rhs, &opt, work.get(), n_work,
+                                               nullptr, 0, infos.data(), stream),
+                    "hdd_operator_solve_batched");
+    for (int32_t j = 0; j < n_rhs; ++j) {
+      const hdd_solve_info& info = infos[size_t(j)];
+      if (info.status != HDD_SOLVE_CONVERGED)
+        throw Stuff::Exceptions::linear_solver_failed(
+            std::string("apply_inverse: linear solver failed for right-hand side ") + std::to_string(j) + " of " +
+            std::to_string(n_rhs) + " (" +
+            (info.status == HDD_SOLVE_MAX_ITER ? "max_iter reached" : "breakdown: the matrix is not positive definite?") +
+            ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) +
+            " iterations, residual " + std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm));
+    }
+    return infos;
+  }
+  std::vector<std::vector<double>> apply_inverse(const std::vector<std::vector<double>>& b, double mu = 0.0,
+                                                 const SolverOptions& options = SolverOptions(),
+                                                 const hdd_block_range* range = nullptr,
+                                                 std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    if (b.empty() || b.size() > size_t(HDD_MAX_VEC))
+      throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC right-hand sides expected");
+    for (const auto& bj : b)
+      if (int64_t(bj.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
+    const int64_t ld = std::max<int64_t>(rows + (rows & 1), 2);
+    internal::DeviceArray<double> db{size_t(ld) * b.size()}, dx{size_t(ld) * b.size()};
+    for (size_t j = 0; j < b.size(); ++j)
+      if (rows)
+        internal::hip_check(hipMemcpy(db.get() + j * size_t(ld), b[j].data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice),
+                            "apply_inverse");
+    const auto i = apply_inverse(db.get(), ld, dx.get(), ld, int32_t(b.size()), mu, options, range);
+    if (infos) *infos = i;
+    const auto all = dx.download();
+    std::vector<std::vector<double>> x(b.size());
+    for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
+    return x;
+  }
   // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
   // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
   void set_tile_mesh(const hdd_mesh& m, std::shared_ptr<internal::DeviceArray<int32_t>> nbrs)
@@ -1064,6 +1123,14 @@ class SWIPDG {
       for (size_t i = 0; i < bmu.size(); ++i) bmu[i] += th * c[i];
     }
     return system_matrix().apply_inverse(bmu, mu, options, nullptr, info);
+  }
+  // ... for several right-hand sides of the caller (1..HDD_MAX_VEC vectors of size() entries) in one batched device
+  // solve: the Riesz representatives of a block of residuals, say.  Column j is bit for bit the single solve's.
+  std::vector<std::vector<double>> solve(const std::vector<std::vector<double>>& b, double mu = 0.0,
+                                         const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                         std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    return system_matrix().apply_inverse(b, mu, options, nullptr, infos);
   }
 
   // base.hh:272-291: only the products requested in the ctor (only_these_products, swipdg.hh:496-508)
@@ -1562,6 +1629,19 @@ class BlockSWIPDG : public SWIPDG {
     const int64_t nb = info_.nb;
     const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
     return system_matrix().apply_inverse(b, mu, options, &rng, info);
+  }
+  // ... for several local right-hand sides on the same get_local_operator(ss) (LRBMS's local corrections) in one
+  // batched device solve
+  std::vector<std::vector<double>> solve_local(int ss, const std::vector<std::vector<double>>& b, double mu = 0.0,
+                                               const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                               std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    range_check(ss);
+    int64_t a, e;
+    internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &e), "range");
+    const int64_t nb = info_.nb;
+    const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
+    return system_matrix().apply_inverse(b, mu, options, &rng, infos);
   }
 
   // block-swipdg.hh:678-685: the local vector of ss (local discretization rhs + boundary contributions) =

@@ -15,7 +15,11 @@ Conjugate gradients need a positive definite matrix, which SWIPDG with the refer
 configuration: the solve on the configuration's own matrix is recorded first ("reference_penalties"),
 and when it breaks down the timing runs on the same mesh, pattern and coefficients with both penalties multiplied by
 --sigma-scale (x4, x16, ... until 200 iterations pass): same bytes, same launches, a definite matrix.
-Prints one JSON line per configuration; --out DIR also writes them to DIR/bench_solve.jsonl."""
+--rhs N measures instead one hdd_operator_solve_batched call on N right-hand sides against N hdd_operator_solve calls
+on the same columns (the unchanged single-solve path), alternating over the rounds in the same process, per iteration
+as above; model per iteration 8 nnz n_comp + (BS + 1) / 2 8 n per group of four columns + 13 8 n per column.
+Prints one JSON line per configuration; --out DIR also writes them to DIR/bench_solve.jsonl (--rhs:
+DIR/bench_solve_batched.jsonl)."""
 import argparse
 import json
 import math
@@ -80,6 +84,59 @@ def build(name, n):
     return H, ctx, loc, dm, dp, assemble, label
 
 
+def run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, scale, gen):
+    """--rhs N: one hdd_operator_solve_batched call on N right-hand sides against N hdd_operator_solve calls (the
+    unchanged single-solve path) on the same columns, alternating over the rounds in this process"""
+    n, nnz, nc, N, iters = dp.t.n_rows, dp.nnz, len(vals), args.rhs, args.iters
+    B = torch.randn((N, n), dtype=torch.float64, device="cuda", generator=gen)
+
+    def batched(k):
+        return H.solve_batched(ctx, dp, vals, B, theta=theta, dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
+
+    def singles(k):
+        return [H.solve(ctx, dp, vals, B[j], theta=theta, dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
+                for j in range(N)]
+
+    def timed(fn, k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(k)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    timed(batched, 3), timed(singles, 3)   # warm-up
+    names = {}
+    ms = dict(batched=[], batched_setup=[], singles=[], singles_setup=[])
+    per = dict(batched=[], singles=[])
+    for _ in range(args.rounds):
+        t, (X, infos) = timed(batched, iters)
+        names["batched"] = H.last_solve_kernels()
+        ms["batched"].append(t)
+        ms["batched_setup"].append(timed(batched, 0)[0])
+        t, one = timed(singles, iters)
+        names["singles"] = H.last_solve_kernels()
+        ms["singles"].append(t)
+        ms["singles_setup"].append(timed(singles, 0)[0])
+        for k in per:
+            per[k].append((ms[k][-1] - ms[k + "_setup"][-1]) / iters)
+    identical = all(bool(torch.equal(X[j].view(torch.int64), one[j][0].view(torch.int64))) for j in range(N))
+    med = {k: float(np.median(v)) for k, v in per.items()}
+    groups = (N + 3) // 4
+    model_b = groups * (8 * nnz * nc + (nb + 1) / 2 * 8 * n) + N * 13 * 8 * n
+    model_s = N * (8 * nnz * nc + (13 + (nb + 1) / 2) * 8 * n)
+    res = dict(config=label, n_rows=n, nnz=nnz, n_comp=nc, block_size=nb, n_rhs=N, iters=iters, rounds=args.rounds,
+               reference_penalties=reference, sigma_scale=scale, kernels=names,
+               status=[i.status for i in infos], iterations=[i.iterations for i in infos],
+               columns_bit_identical_to_singles=identical,
+               ms={k: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v))) for k, v in ms.items()},
+               ms_per_iteration={k: dict(median=med[k], min=float(min(v)), max=float(max(v))) for k, v in per.items()},
+               batched_over_singles=med["batched"] / med["singles"],
+               model_bytes_per_iteration=dict(batched=model_b, singles=model_s), model_ratio=model_b / model_s,
+               model_GBps=dict(batched=model_b / med["batched"] / 1e6, singles=model_s / med["singles"] / 1e6))
+    print(json.dumps(res), flush=True)
+
+
 def run_config(args):
     import torch
     torch.cuda.set_device(0)
@@ -97,6 +154,8 @@ def run_config(args):
         scale *= args.sigma_scale
         vals = assemble(scale, vals)
         _, i0 = H.solve(ctx, dp, vals, b, theta=theta, dmesh=dm, rtol=0.0, max_iter=iters, check_every=iters)
+    if args.rhs:
+        return run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, scale, gen)
     Dinv = inverse_blocks(torch, loc, dm, dp, vals, theta)
 
     def fused(k):
@@ -167,6 +226,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sigma-scale", type=float, default=4.0, help="penalty factor per step when the solve breaks down")
     ap.add_argument("--converge", type=int, default=0, help="also solve to rtol 1e-8 with at most this many iterations")
+    ap.add_argument("--rhs", type=int, default=0, help="N > 0: time one batched solve of N right-hand sides against N single "
+                    "solves instead (bench_solve_batched.jsonl)")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per configuration (child process)")
     ap.add_argument("--out", default=None, help="directory for bench_solve.jsonl")
     args = ap.parse_args()
@@ -176,7 +237,7 @@ def main():
     lines = []
     for c in args.configs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--n", str(args.n), "--iters", str(args.iters),
-               "--rounds", str(args.rounds), "--converge", str(args.converge), "--sigma-scale", str(args.sigma_scale)]
+               "--rounds", str(args.rounds), "--converge", str(args.converge), "--sigma-scale", str(args.sigma_scale), "--rhs", str(args.rhs)]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
@@ -191,7 +252,7 @@ def main():
                 print(ln, flush=True)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, "bench_solve.jsonl"), "w") as f:
+        with open(os.path.join(args.out, "bench_solve_batched.jsonl" if args.rhs else "bench_solve.jsonl"), "w") as f:
             f.write("\n".join(lines) + "\n")
     return 0
 
