@@ -10,14 +10,14 @@
 //   cg_direction_kernel       sums the partials, beta = rho' / rho, p = z + beta p; one lane of workgroup 0 writes
 //                             the state and history[k + 1]
 // The state (SolveState) lives in the caller's workspace.  rho is double-buffered by the parity of k and the stop word
-// done_at is the iteration count at which the solve ended (INT32_MAX while running): the workgroups of launch k that
-// read the state while workgroup 0 writes it decide the same either way (done_at <= k is false for the old and for
-// the new value k + 1; a breakdown is detected by every workgroup from the same sums).  A launch of iteration k
-// returns at once when done_at <= k, so the host may enqueue any number of iterations between two looks.
+// done_at is the iteration count at which the solve ended (SOLVE_RUNNING until then; why the workgroups of a launch
+// may read it while one lane writes it: solve_direction_column).  A launch of iteration k returns at once when
+// done_at <= k, so the host may enqueue any number of iterations between two looks.
 // Every sum is two-stage in a fixed order: bit-identical from call to call, and independent of check_every.
 // The build has -ffinite-math-only: non-finite scalars are recognised by their bits, behind an optimisation barrier
 // (solve_finite).
-// Several right-hand sides per call (hdd_operator_solve_batched): the section at the end of this file.
+// The steps of one column -- solve_init_column, solve_update_block, solve_direction_column -- are shared with the
+// kernels for several right-hand sides per call (hdd_operator_solve_batched), the section at the end of this file.
 #pragma once
 #include <cstdint>
 
@@ -28,6 +28,7 @@ namespace dev {
 
 constexpr int SOLVE_PARTS = 4096;    // most partial sums of one kind (workgroups of the launch that wrote them)
 constexpr int SOLVE_FLAG_ZERO_RHS = 1;
+constexpr int32_t SOLVE_RUNNING = 0x7fffffff;   // done_at / the group's stop word while iterating
 
 struct SolveState {
   double rho[2];       // r . z, indexed by the parity of the iteration that reads it
@@ -121,13 +122,18 @@ __device__ __forceinline__ void solve_store(double* p, const double (&v)[BS])
   }
 }
 
-// z = D^-1 r from the packed lower triangle of the (symmetric) inverse block
+// the packed lower triangle of one (symmetric) inverse block
 template <int BS>
-__device__ __forceinline__ void solve_precond(const double* dinv, const double (&r)[BS], double (&z)[BS])
+__device__ __forceinline__ void solve_load_packed(const double* dinv, double (&m)[solve_packed<BS>()])
 {
-  double m[solve_packed<BS>()];
 #pragma unroll
   for (int k = 0; k < solve_packed<BS>(); ++k) m[k] = dinv[k];
+}
+
+// z = D^-1 r from the packed inverse block in registers
+template <int BS>
+__device__ __forceinline__ void solve_precond_regs(const double (&m)[solve_packed<BS>()], const double (&r)[BS], double (&z)[BS])
+{
 #pragma unroll
   for (int i = 0; i < BS; ++i) {
     double s = 0.0;
@@ -135,6 +141,13 @@ __device__ __forceinline__ void solve_precond(const double* dinv, const double (
     for (int j = 0; j < BS; ++j) s = __builtin_fma(i >= j ? m[i * (i + 1) / 2 + j] : m[j * (j + 1) / 2 + i], r[j], s);
     z[i] = s;
   }
+}
+template <int BS>
+__device__ __forceinline__ void solve_precond(const double* dinv, const double (&r)[BS], double (&z)[BS])
+{
+  double m[solve_packed<BS>()];
+  solve_load_packed<BS>(dinv, m);
+  solve_precond_regs<BS>(m, r, z);
 }
 
 // In-place inverse of a symmetric positive definite block (Gauss-Jordan without pivoting: the pivots are the Schur
@@ -283,15 +296,11 @@ __global__ void __launch_bounds__(256) cg_init_kernel(const SolveVectors v, cons
   }
 }
 
-// Setup, one wave: the state before the first iteration.  n_bad: partial counts of indefinite blocks in part_pq
-__global__ void __launch_bounds__(64) cg_init_state_kernel(const SolveVectors v, int n_parts, int n_bad, double rtol, double atol)
+// One column's state before the first iteration and history[0] (nullable), by one lane; bad: the number of
+// indefinite diagonal blocks.  Returns done_at: 0 when the column does not iterate.
+__device__ __forceinline__ int solve_init_column(SolveState& s, double* history, double bad, double bb, double rz, double rr,
+                                                 double rtol, double atol)
 {
-  const double bad = solve_wave_sum(v.part_pq, n_bad);
-  const double bb = solve_wave_sum(v.part_bb, n_parts);
-  const double rz = solve_wave_sum(v.part_rz, n_parts);
-  const double rr = solve_wave_sum(v.part_rr, n_parts);
-  if (threadIdx.x != 0) return;
-  SolveState& s = *v.state;
   const double t = rtol * __builtin_sqrt(bb);
   const double thresh = t > atol ? t : atol;
   s.rho[0] = rz;
@@ -303,14 +312,52 @@ __global__ void __launch_bounds__(64) cg_init_state_kernel(const SolveVectors v,
   const bool zero_rhs = solve_is_zero(bb);
   s.flags = zero_rhs ? SOLVE_FLAG_ZERO_RHS : 0;
   s.pad = 0.0;
-  int status = HDD_SOLVE_CONVERGED, done_at = 0x7fffffff;
+  int status = HDD_SOLVE_CONVERGED, done_at = SOLVE_RUNNING;
   if (zero_rhs) done_at = 0;                                      // x = 0 (the host clears it)
   else if (bad > 0.0) status = HDD_SOLVE_BREAKDOWN, done_at = 0;  // a diagonal block is not positive definite
   else if (solve_finite(rr) && rr <= s.thresh2) done_at = 0;
   else if (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0)) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
   s.status = status;
   s.done_at = done_at;
-  if (v.history) v.history[0] = __builtin_sqrt(rr);
+  if (history) history[0] = __builtin_sqrt(rr);
+  return done_at;
+}
+
+// Setup, one wave: the state before the first iteration.  n_bad: partial counts of indefinite blocks in part_pq
+__global__ void __launch_bounds__(64) cg_init_state_kernel(const SolveVectors v, int n_parts, int n_bad, double rtol, double atol)
+{
+  const double bad = solve_wave_sum(v.part_pq, n_bad);
+  const double bb = solve_wave_sum(v.part_bb, n_parts);
+  const double rz = solve_wave_sum(v.part_rz, n_parts);
+  const double rr = solve_wave_sum(v.part_rr, n_parts);
+  if (threadIdx.x == 0) solve_init_column(*v.state, v.history, bad, bb, rz, rr, rtol, atol);
+}
+
+// One block of BS rows of one column (p, q, x, r, z point at it): x += alpha p, r -= alpha q, z = D^-1 r from the
+// packed inverse block m (not read without PRE), r . z and r . r added to rz (PRE) and rr
+template <int BS, bool PRE, bool A16>
+__device__ __forceinline__ void solve_update_block(const double* p, const double* q, double* x, double* r, double* z,
+                                                   const double (&m)[solve_packed<BS>()], double alpha, double& rz, double& rr)
+{
+  double pv[BS], qv[BS], xv[BS], rv[BS], zv[BS];
+  solve_load<BS, A16>(p, pv);
+  solve_load<BS, A16>(q, qv);
+  solve_load<BS, A16>(x, xv);
+  solve_load<BS, A16>(r, rv);
+#pragma unroll
+  for (int j = 0; j < BS; ++j) {
+    xv[j] = __builtin_fma(alpha, pv[j], xv[j]);
+    rv[j] = __builtin_fma(-alpha, qv[j], rv[j]);
+  }
+  if constexpr (PRE) solve_precond_regs<BS>(m, rv, zv);
+#pragma unroll
+  for (int j = 0; j < BS; ++j) {
+    if constexpr (PRE) rz = __builtin_fma(rv[j], zv[j], rz);
+    rr = __builtin_fma(rv[j], rv[j], rr);
+  }
+  solve_store<BS, A16>(x, xv);
+  solve_store<BS, A16>(r, rv);
+  if constexpr (PRE) solve_store<BS, A16>(z, zv);
 }
 
 template <int BS, bool PRE, bool A16>
@@ -325,25 +372,9 @@ __global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, in
   const int64_t n_blk = v.n / BS;
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
     const int64_t o = i * BS;
-    double pv[BS], qv[BS], xv[BS], rv[BS], zv[BS];
-    solve_load<BS, A16>(v.p + o, pv);
-    solve_load<BS, A16>(v.q + o, qv);
-    solve_load<BS, A16>(v.x + o, xv);
-    solve_load<BS, A16>(v.r + o, rv);
-#pragma unroll
-    for (int j = 0; j < BS; ++j) {
-      xv[j] = __builtin_fma(alpha, pv[j], xv[j]);
-      rv[j] = __builtin_fma(-alpha, qv[j], rv[j]);
-    }
-    if constexpr (PRE) solve_precond<BS>(v.dinv + i * solve_packed<BS>(), rv, zv);
-#pragma unroll
-    for (int j = 0; j < BS; ++j) {
-      if constexpr (PRE) rz = __builtin_fma(rv[j], zv[j], rz);
-      rr = __builtin_fma(rv[j], rv[j], rr);
-    }
-    solve_store<BS, A16>(v.x + o, xv);
-    solve_store<BS, A16>(v.r + o, rv);
-    if constexpr (PRE) solve_store<BS, A16>(v.z + o, zv);
+    [[maybe_unused]] double m[solve_packed<BS>()];
+    if constexpr (PRE) solve_load_packed<BS>(v.dinv + i * solve_packed<BS>(), m);
+    solve_update_block<BS, PRE, A16>(v.p + o, v.q + o, v.x + o, v.r + o, v.z + o, m, alpha, rz, rr);
   }
   const double s0 = solve_block_sum(rz, red[0]), s1 = solve_block_sum(rr, red[1]);
   if (threadIdx.x == 0) {
@@ -352,34 +383,49 @@ __global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, in
   }
 }
 
-// n_parts: workgroups of the cg_update launch
+// The end of iteration k for one column that was live (done_at > k) when the launch began: sums the partials
+// (n_parts: workgroups of the cg_update launch), decides, p = z + beta p; the writer (one lane of the launch) stores
+// the state and history[k + 1] (history: the column's, nullable).  Returns the column's done_at after this launch:
+// k (p . q breakdown: x, r are those of iteration k), k + 1 (converged / r . z breakdown) or SOLVE_RUNNING.
+// The other workgroups of launch k read done_at while the writer stores it, and decide the same for the old value
+// SOLVE_RUNNING and for the new one: `<= k` is false for k + 1 as well; and a reader of the old value before a new k
+// forms the same p . q from the same partial sums and leaves the column alone, too.  The launches before (apply,
+// update of iteration k) and after (iteration k + 1) are ordered by the stream.
 template <bool PRE>
-__global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v, int k, int n_parts)
+__device__ __forceinline__ int solve_direction_column(SolveState& s, const double* part_pq, int n_pq, const double* part_rz,
+                                                      const double* part_rr, int n_parts, double* p, const double* z, int64_t n,
+                                                      double* history, int k, bool writer)
 {
-  SolveState& s = *v.state;
-  if (s.done_at <= k) return;   // (uniform)
-  const bool writer = blockIdx.x == 0 && threadIdx.x == 0;
-  const double pq = solve_wave_sum(v.part_pq, v.n_pq);
-  if (!solve_finite(pq) || !(pq > 0.0)) {   // x, r are those of iteration k
+  const double pq = solve_wave_sum(part_pq, n_pq);
+  if (!solve_finite(pq) || !(pq > 0.0)) {
     if (writer) s.status = HDD_SOLVE_BREAKDOWN, s.done_at = k;
-    return;
+    return k;
   }
-  const double rr = solve_wave_sum(v.part_rr, n_parts);
-  const double rz = PRE ? solve_wave_sum(v.part_rz, n_parts) : rr;
+  const double rr = solve_wave_sum(part_rr, n_parts);
+  const double rz = PRE ? solve_wave_sum(part_rz, n_parts) : rr;
   const bool converged = solve_finite(rr) && rr <= s.thresh2;
   const bool broken = !converged && (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0));
   if (writer) {
     s.rho[(k + 1) & 1] = rz;
     s.rr = rr;
     s.iteration = k + 1;
-    if (v.history) v.history[k + 1] = __builtin_sqrt(rr);
+    if (history) history[k + 1] = __builtin_sqrt(rr);
     if (broken) s.status = HDD_SOLVE_BREAKDOWN;
     if (converged || broken) s.done_at = k + 1;
   }
-  if (converged || broken) return;
+  if (converged || broken) return k + 1;
   const double beta = rz / s.rho[k & 1];
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < v.n; i += int64_t(gridDim.x) * 256)
-    v.p[i] = __builtin_fma(beta, v.p[i], v.z[i]);
+  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
+    p[i] = __builtin_fma(beta, p[i], z[i]);
+  return SOLVE_RUNNING;
+}
+
+template <bool PRE>
+__global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v, int k, int n_parts)
+{
+  if (v.state->done_at <= k) return;   // (uniform)
+  solve_direction_column<PRE>(*v.state, v.part_pq, v.n_pq, v.part_rz, v.part_rr, n_parts, v.p, v.z, v.n, v.history, k,
+                              blockIdx.x == 0 && threadIdx.x == 0);
 }
 
 // ---- several right-hand sides per call (hdd_operator_solve_batched) ----------------------------------------------
@@ -388,19 +434,9 @@ __global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v,
 // the arithmetic of the single solve -- its own FMA chains, its own partial sums [column][workgroup] on the single
 // solve's grids, its own SolveState -- so column j ends with the bits hdd_operator_solve gives for (b_j, x0_j).
 //
-// Two kinds of stop words.  state[c].done_at is column c's (as above): a column that is done is frozen, no later
-// launch touches its x, r, z or p (the apply still writes its q, which nobody reads).  *stop is the group's: the
-// iteration at which its last live column ended (INT32_MAX while one is live); a launch of iteration k returns at
-// once when *stop <= k.  Only cg_direction_batched_kernel writes either word during the iteration, one lane of
-// workgroup 0, while the other workgroups of the same launch k read them -- and decide the same for the old and
-// for the new value:
-//   done_at[c]  old INT32_MAX, new k + 1 (converged / r . z breakdown): `<= k` is false both ways.  New k (p . q
-//               breakdown): a reader of the old value forms the same p . q from the same partial sums and skips the
-//               column as well.
-//   *stop       old INT32_MAX, new the largest done_at of the group, which is k + 1 (false both ways) unless every
-//               column that was still live broke down on its p . q in this launch (new value <= k): a reader of the
-//               old value then finds every column done or broken and touches nothing either.
-// The launches before (apply, update of iteration k) and after (iteration k + 1) are ordered by the stream.
+// Two kinds of stop words.  state[c].done_at is column c's (solve_direction_column): a column that is done is frozen,
+// no later launch touches its x, r, z or p (the apply still writes its q, which nobody reads).  *stop is the group's
+// (cg_direction_batched_kernel): a launch of iteration k returns at once when *stop <= k.
 
 struct SolveBatch {
   SolveState* state;                    // [nv], the group's columns
@@ -417,21 +453,8 @@ struct SolveBatch {
   int64_t ldh;
 };
 
-// z = D^-1 r from the packed inverse block already in registers: the arithmetic of solve_precond
-template <int BS>
-__device__ __forceinline__ void solve_precond_regs(const double (&m)[BS * (BS + 1) / 2], const double (&r)[BS], double (&z)[BS])
-{
-#pragma unroll
-  for (int i = 0; i < BS; ++i) {
-    double s = 0.0;
-#pragma unroll
-    for (int j = 0; j < BS; ++j) s = __builtin_fma(i >= j ? m[i * (i + 1) / 2 + j] : m[j * (j + 1) / 2 + i], r[j], s);
-    z[i] = s;
-  }
-}
-
 // Setup, one wave: the states of all n_rhs columns before the first iteration (cg_init_state_kernel's sums and
-// decisions per column; the partial sums are [column][n_parts]), then the stop words of the groups of APPLY_NV
+// solve_init_column per column; the partial sums are [column][n_parts]), then the stop words of the groups of APPLY_NV
 __global__ void __launch_bounds__(64) cg_init_state_batched_kernel(SolveState* state, int32_t* stop, int n_rhs, const double* part_bad,
                                                                    int n_bad, const double* part_bb, const double* part_rz,
                                                                    const double* part_rr, int n_parts, double rtol, double atol,
@@ -444,30 +467,10 @@ __global__ void __launch_bounds__(64) cg_init_state_batched_kernel(SolveState* s
     const double rz = solve_wave_sum(part_rz + int64_t(c) * n_parts, n_parts);
     const double rr = solve_wave_sum(part_rr + int64_t(c) * n_parts, n_parts);
     if (threadIdx.x != 0) continue;
-    SolveState& s = state[c];
-    const double t = rtol * __builtin_sqrt(bb);
-    const double thresh = t > atol ? t : atol;
-    s.rho[0] = rz;
-    s.rho[1] = 0.0;
-    s.rr = rr;
-    s.bb = bb;
-    s.thresh2 = thresh * thresh;
-    s.iteration = 0;
-    const bool zero_rhs = solve_is_zero(bb);
-    s.flags = zero_rhs ? SOLVE_FLAG_ZERO_RHS : 0;
-    s.pad = 0.0;
-    int status = HDD_SOLVE_CONVERGED, done_at = 0x7fffffff;
-    if (zero_rhs) done_at = 0;
-    else if (bad > 0.0) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
-    else if (solve_finite(rr) && rr <= s.thresh2) done_at = 0;
-    else if (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0)) status = HDD_SOLVE_BREAKDOWN, done_at = 0;
-    s.status = status;
-    s.done_at = done_at;
-    if (done_at != 0) live |= 1u << c;
-    if (history) history[int64_t(c) * ldh] = __builtin_sqrt(rr);
+    if (solve_init_column(state[c], history ? history + int64_t(c) * ldh : nullptr, bad, bb, rz, rr, rtol, atol) != 0) live |= 1u << c;
   }
   if (threadIdx.x != 0) return;
-  for (int g = 0; g * APPLY_NV < n_rhs; ++g) stop[g] = ((live >> (g * APPLY_NV)) & ((1u << APPLY_NV) - 1)) ? 0x7fffffff : 0;
+  for (int g = 0; g * APPLY_NV < n_rhs; ++g) stop[g] = ((live >> (g * APPLY_NV)) & ((1u << APPLY_NV) - 1)) ? SOLVE_RUNNING : 0;
 }
 
 // cg_update_kernel for a group: the grid and the lane -> block mapping are the single solve's; the lane loads its
@@ -501,33 +504,12 @@ __global__ void __launch_bounds__(256) cg_update_batched_kernel(const SolveBatch
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
     const int64_t o = i * BS;
     [[maybe_unused]] double m[solve_packed<BS>()];
-    if constexpr (PRE) {
-#pragma unroll
-      for (int j = 0; j < solve_packed<BS>(); ++j) m[j] = v.dinv[i * solve_packed<BS>() + j];
-    }
+    if constexpr (PRE) solve_load_packed<BS>(v.dinv + i * solve_packed<BS>(), m);
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       if (!live[c]) continue;
       const int64_t ow = c * v.ldw + o, ox = c * v.ldx + o;
-      double pv[BS], qv[BS], xv[BS], rv[BS], zv[BS];
-      solve_load<BS, A16>(v.p + ow, pv);
-      solve_load<BS, A16>(v.q + ow, qv);
-      solve_load<BS, A16>(v.x + ox, xv);
-      solve_load<BS, A16>(v.r + ow, rv);
-#pragma unroll
-      for (int j = 0; j < BS; ++j) {
-        xv[j] = __builtin_fma(alpha[c], pv[j], xv[j]);
-        rv[j] = __builtin_fma(-alpha[c], qv[j], rv[j]);
-      }
-      if constexpr (PRE) solve_precond_regs<BS>(m, rv, zv);
-#pragma unroll
-      for (int j = 0; j < BS; ++j) {
-        if constexpr (PRE) rz[c] = __builtin_fma(rv[j], zv[j], rz[c]);
-        rr[c] = __builtin_fma(rv[j], rv[j], rr[c]);
-      }
-      solve_store<BS, A16>(v.x + ox, xv);
-      solve_store<BS, A16>(v.r + ow, rv);
-      if constexpr (PRE) solve_store<BS, A16>(v.z + ow, zv);
+      solve_update_block<BS, PRE, A16>(v.p + ow, v.q + ow, v.x + ox, v.r + ow, v.z + ow, m, alpha[c], rz[c], rr[c]);
     }
   }
 #pragma unroll
@@ -541,8 +523,12 @@ __global__ void __launch_bounds__(256) cg_update_batched_kernel(const SolveBatch
   }
 }
 
-// cg_direction_kernel for a group; n_parts: workgroups of the cg_update launch.  The race argument is at the top
-// of this section.
+// cg_direction_kernel for a group: solve_direction_column for every live column, then the group's stop word -- the
+// iteration at which its last live column ended (SOLVE_RUNNING while one is live), written by the same lane that
+// writes the columns' done_at while the other workgroups of launch k read it.  They decide the same for the old
+// value SOLVE_RUNNING and for the new one, the largest done_at of the group: that is k + 1 (`<= k` false both ways)
+// unless every column that was still live broke down on its p . q in this launch (new value <= k), and a reader of
+// the old value then finds every column done or broken and touches nothing either.
 template <bool PRE, int NV>
 __global__ void __launch_bounds__(256) cg_direction_batched_kernel(const SolveBatch v, int k, int n_parts)
 {
@@ -553,40 +539,13 @@ __global__ void __launch_bounds__(256) cg_direction_batched_kernel(const SolveBa
 #pragma unroll
   for (int c = 0; c < NV; ++c) {
     if (c >= v.nv) continue;
-    SolveState& s = v.state[c];
-    const int d = s.done_at;
-    if (d <= k) {   // frozen
-      ended = ended > d ? ended : d;
-      continue;
-    }
-    const double pq = solve_wave_sum(v.part_pq + int64_t(c) * v.n_pq, v.n_pq);
-    if (!solve_finite(pq) || !(pq > 0.0)) {   // x, r are those of iteration k
-      if (writer) s.status = HDD_SOLVE_BREAKDOWN, s.done_at = k;
-      ended = ended > k ? ended : k;
-      continue;
-    }
-    const double rr = solve_wave_sum(v.part_rr + int64_t(c) * n_parts, n_parts);
-    const double rz = PRE ? solve_wave_sum(v.part_rz + int64_t(c) * n_parts, n_parts) : rr;
-    const bool converged = solve_finite(rr) && rr <= s.thresh2;
-    const bool broken = !converged && (!solve_finite(rr) || !solve_finite(rz) || !(rz > 0.0));
-    if (writer) {
-      s.rho[(k + 1) & 1] = rz;
-      s.rr = rr;
-      s.iteration = k + 1;
-      if (v.history) v.history[c * v.ldh + k + 1] = __builtin_sqrt(rr);
-      if (broken) s.status = HDD_SOLVE_BREAKDOWN;
-      if (converged || broken) s.done_at = k + 1;
-    }
-    if (converged || broken) {
-      ended = k + 1;
-      continue;
-    }
-    any = true;
-    const double beta = rz / s.rho[k & 1];
-    double* p = v.p + c * v.ldw;
-    const double* z = v.z + c * v.ldw;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < v.n; i += int64_t(gridDim.x) * 256)
-      p[i] = __builtin_fma(beta, p[i], z[i]);
+    int d = v.state[c].done_at;   // <= k: frozen
+    if (d > k)
+      d = solve_direction_column<PRE>(v.state[c], v.part_pq + int64_t(c) * v.n_pq, v.n_pq, v.part_rz + int64_t(c) * n_parts,
+                                      v.part_rr + int64_t(c) * n_parts, n_parts, v.p + c * v.ldw, v.z + c * v.ldw, v.n,
+                                      v.history ? v.history + c * v.ldh : nullptr, k, writer);
+    if (d == SOLVE_RUNNING) any = true;
+    else ended = ended > d ? ended : d;
   }
   if (writer && !any) *v.stop = ended;
 }

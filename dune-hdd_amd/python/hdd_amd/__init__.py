@@ -944,67 +944,20 @@ def apply2(ctx, dpattern, vals, v, u, theta=None, dmesh=None, block=None, stream
 _PRECONDS = {"none": PRECOND_NONE, "block_jacobi": PRECOND_BLOCK_JACOBI}
 
 
-def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, rtol=1e-8, atol=0.0, max_iter=10000,
-          precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None, grid=None):
-    """hdd_operator_solve: x with (sum_q theta[q] A_q) x = b by (block-)Jacobi preconditioned conjugate gradients on
-    the device -- the apply_inverse of uncached_solve.  Operands as apply's; block: None or a square diagonal block
-    ((ss, ss): the local solve on get_local_operator(ss)).  THE MATRIX MUST BE SYMMETRIC POSITIVE DEFINITE (hdd.h).
-    b: device float64 [rows] (unit stride); x0: the initial guess or None (zero).  block_size 0: nb of dmesh (of the
-    pattern's LocalMesh when dmesh is None; precond="none" without either: 1).  Returns (x, info): info a SolveInfo
-    (status SOLVE_*, iterations, residual, rhs_norm) that also carries .history (device [iterations + 1], ||r_k||) when
-    history=True.  Synchronises the stream at every look (check_every iterations, default 32)."""
+def _solve_operands(batched, dpattern, vals, theta, dmesh, block, grid, B, X0, rtol, atol, max_iter, precond, block_size,
+                    check_every, stream):
+    """what solve (B = b [rows], X0 = x0) and solve_batched (B [n_rhs, rows]) share: apply's operands as the leading
+    arguments of the ABI call (keep: what they point into), the checks of B and X0, the implied block_size, X (the
+    copy of X0, or empty), the options and the stream"""
     torch = _torch()
+    who = "solve_batched" if batched else "solve"
     vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
     if precond not in _PRECONDS:
-        raise HddError("solve: precond is one of %s" % sorted(_PRECONDS))
-    if b.dtype != torch.float64 or b.dim() != 1 or b.shape[0] != rows or (rows > 1 and b.stride(0) != 1):
-        raise HddError("solve: b must be float64 [%d] with unit stride" % rows)
-    block_size = int(block_size)
-    if block_size == 0 and dmesh is None:
-        local = getattr(dpattern, "local", None)
-        if local is not None and not getattr(dpattern, "volume", False) and local.nb <= 8:
-            block_size = int(local.nb)
-        elif precond == "none":
-            block_size = 1
-    flags = 0
-    if x0 is None:
-        x = torch.empty(rows, dtype=torch.float64, device=b.device)
-    else:
-        if x0.dtype != torch.float64 or x0.shape != b.shape:
-            raise HddError("solve: x0 must be float64 [%d]" % rows)
-        x = x0.to(b.device, copy=True).contiguous()
-        flags |= SOLVE_X0
-    opt = SolveOptions(float(rtol), float(atol), int(max_iter), int(check_every), _PRECONDS[precond], block_size, flags, 0)
-    n_work = max(int(lib().hdd_operator_solve_workspace(rows, block_size)), 1)
-    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
-    hist = torch.zeros(max(int(max_iter), 0) + 1, dtype=torch.float64, device=b.device) if history else None
-    info = SolveInfo()
-    s = stream if stream is not None else torch.cuda.current_stream(b.device).cuda_stream
-    _check(lib().hdd_operator_solve(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
-                                    n, _p(th), None if rng is None else C.addressof(rng), b.data_ptr(), x.data_ptr(),
-                                    C.addressof(opt), work.data_ptr(), n_work,
-                                    None if hist is None else hist.data_ptr(), C.addressof(info), C.c_void_p(s)),
-           "hdd_operator_solve")
-    info.history = None if hist is None else hist[:info.iterations + 1]
-    return x, info
-
-
-def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0=None, rtol=1e-8, atol=0.0,
-                  max_iter=10000, precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None,
-                  grid=None):
-    """hdd_operator_solve_batched: solve()'s system for the n_rhs (1..MAX_VEC) rows of B at once -- pyMOR's
-    apply_inverse on a VectorArray.  B: device float64 [n_rhs, rows] with unit inner stride (its row stride is ldb);
-    X0: per-column initial guesses of B's shape, or None.  Every other argument is solve()'s and holds for all
-    columns.  Returns (X, infos): X [n_rhs, rows], infos a list of SolveInfo (each with .history when history=True).
-    Column j is bit for bit what solve() gives for (B[j], X0[j]); the value arrays and the inverse blocks are read
-    once per group of four columns and iteration."""
-    torch = _torch()
-    vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
-    if precond not in _PRECONDS:
-        raise HddError("solve_batched: precond is one of %s" % sorted(_PRECONDS))
-    if B.dtype != torch.float64 or B.dim() != 2 or B.shape[1] != rows or (rows > 1 and B.stride(1) != 1):
-        raise HddError("solve_batched: B must be float64 [n_rhs, %d] with unit inner stride" % rows)
-    n_rhs = int(B.shape[0])
+        raise HddError("%s: precond is one of %s" % (who, sorted(_PRECONDS)))
+    if B.dtype != torch.float64 or B.dim() != 1 + batched or B.shape[-1] != rows or (rows > 1 and B.stride(-1) != 1):
+        raise HddError("solve_batched: B must be float64 [n_rhs, %d] with unit inner stride" % rows if batched
+                       else "solve: b must be float64 [%d] with unit stride" % rows)
+    n_rhs = int(B.shape[0]) if batched else 1
     if not 1 <= n_rhs <= MAX_VEC:
         raise HddError("solve_batched: n_rhs outside 1..%d" % MAX_VEC)
     ldb = int(B.stride(0)) if n_rhs > 1 else max(rows, 1)
@@ -1019,24 +972,62 @@ def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0
             block_size = 1
     flags = 0
     if X0 is None:
-        X = torch.empty((n_rhs, rows), dtype=torch.float64, device=B.device)
+        X = torch.empty(B.shape, dtype=torch.float64, device=B.device)
     else:
         if X0.dtype != torch.float64 or X0.shape != B.shape:
-            raise HddError("solve_batched: X0 must be float64 [%d, %d]" % (n_rhs, rows))
+            raise HddError("solve_batched: X0 must be float64 [%d, %d]" % (n_rhs, rows) if batched
+                           else "solve: x0 must be float64 [%d]" % rows)
         X = X0.to(B.device, copy=True).contiguous()
         flags |= SOLVE_X0
     opt = SolveOptions(float(rtol), float(atol), int(max_iter), int(check_every), _PRECONDS[precond], block_size, flags, 0)
-    n_work = max(int(lib().hdd_operator_solve_batched_workspace(rows, block_size, n_rhs)), 1)
+    s = stream if stream is not None else torch.cuda.current_stream(B.device).cuda_stream
+    operator = (None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs, n, _p(th),
+                None if rng is None else C.addressof(rng))
+    return operator, (th, rng), rows, n_rhs, ldb, X, opt, C.c_void_p(s)
+
+
+def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, rtol=1e-8, atol=0.0, max_iter=10000,
+          precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None, grid=None):
+    """hdd_operator_solve: x with (sum_q theta[q] A_q) x = b by (block-)Jacobi preconditioned conjugate gradients on
+    the device -- the apply_inverse of uncached_solve.  Operands as apply's; block: None or a square diagonal block
+    ((ss, ss): the local solve on get_local_operator(ss)).  THE MATRIX MUST BE SYMMETRIC POSITIVE DEFINITE (hdd.h).
+    b: device float64 [rows] (unit stride); x0: the initial guess or None (zero).  block_size 0: nb of dmesh (of the
+    pattern's LocalMesh when dmesh is None; precond="none" without either: 1).  Returns (x, info): info a SolveInfo
+    (status SOLVE_*, iterations, residual, rhs_norm) that also carries .history (device [iterations + 1], ||r_k||) when
+    history=True.  Synchronises the stream at every look (check_every iterations, default 32)."""
+    torch = _torch()
+    operator, keep, rows, _, _, x, opt, s = _solve_operands(False, dpattern, vals, theta, dmesh, block, grid, b, x0, rtol, atol,
+                                                            max_iter, precond, block_size, check_every, stream)
+    n_work = max(int(lib().hdd_operator_solve_workspace(rows, opt.block_size)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
+    hist = torch.zeros(max(int(max_iter), 0) + 1, dtype=torch.float64, device=b.device) if history else None
+    info = SolveInfo()
+    _check(lib().hdd_operator_solve(ctx.h, *operator, b.data_ptr(), x.data_ptr(), C.addressof(opt), work.data_ptr(), n_work,
+                                    None if hist is None else hist.data_ptr(), C.addressof(info), s), "hdd_operator_solve")
+    info.history = None if hist is None else hist[:info.iterations + 1]
+    return x, info
+
+
+def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0=None, rtol=1e-8, atol=0.0,
+                  max_iter=10000, precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None,
+                  grid=None):
+    """hdd_operator_solve_batched: solve()'s system for the n_rhs (1..MAX_VEC) rows of B at once -- pyMOR's
+    apply_inverse on a VectorArray.  B: device float64 [n_rhs, rows] with unit inner stride (its row stride is ldb);
+    X0: per-column initial guesses of B's shape, or None.  Every other argument is solve()'s and holds for all
+    columns.  Returns (X, infos): X [n_rhs, rows], infos a list of SolveInfo (each with .history when history=True).
+    Column j is bit for bit what solve() gives for (B[j], X0[j]); the value arrays and the inverse blocks are read
+    once per group of four columns and iteration."""
+    torch = _torch()
+    operator, keep, rows, n_rhs, ldb, X, opt, s = _solve_operands(True, dpattern, vals, theta, dmesh, block, grid, B, X0, rtol, atol,
+                                                                  max_iter, precond, block_size, check_every, stream)
+    n_work = max(int(lib().hdd_operator_solve_batched_workspace(rows, opt.block_size, n_rhs)), 1)
     work = torch.empty(n_work, dtype=torch.float64, device=B.device)
     ldh = max(int(max_iter), 0) + 1
     hist = torch.zeros((n_rhs, ldh), dtype=torch.float64, device=B.device) if history else None
     infos = (SolveInfo * n_rhs)()
-    s = stream if stream is not None else torch.cuda.current_stream(B.device).cuda_stream
-    _check(lib().hdd_operator_solve_batched(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t),
-                                            ptrs, n, _p(th), None if rng is None else C.addressof(rng), B.data_ptr(), ldb,
-                                            X.data_ptr(), max(rows, 1), n_rhs, C.addressof(opt), work.data_ptr(), n_work,
-                                            None if hist is None else hist.data_ptr(), ldh, C.addressof(infos),
-                                            C.c_void_p(s)), "hdd_operator_solve_batched")
+    _check(lib().hdd_operator_solve_batched(ctx.h, *operator, B.data_ptr(), ldb, X.data_ptr(), max(rows, 1), n_rhs,
+                                            C.addressof(opt), work.data_ptr(), n_work, None if hist is None else hist.data_ptr(),
+                                            ldh, C.addressof(infos), s), "hdd_operator_solve_batched")
     out = []
     for j in range(n_rhs):
         i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)

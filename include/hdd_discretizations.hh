@@ -718,21 +718,14 @@ class AffinelyDecomposedMatrix {
     operands(mu, v, theta);
     const hdd_csr pat = pattern->csr();
     const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
-    hdd_solve_options opt{options.rtol, options.atol, options.max_iter, options.check_every, options.precond,
-                          options.block_size, x0 ? HDD_SOLVE_X0 : 0, 0};
-    if (opt.block_size == 0 && !tile_nbrs) opt.block_size = 1;
+    const hdd_solve_options opt = solve_options(options, x0);
     const int64_t n_work = std::max<int64_t>(hdd_operator_solve_workspace(rows, opt.block_size), 1);
     internal::DeviceArray<double> work{size_t(n_work)};
     hdd_solve_info info{};
     internal::check(hdd_operator_solve(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
                                        theta.data(), range, d_b, d_x, &opt, work.get(), n_work, nullptr, &info, stream),
                     "hdd_operator_solve");
-    if (info.status != HDD_SOLVE_CONVERGED)
-      throw Stuff::Exceptions::linear_solver_failed(
-          std::string("apply_inverse: linear solver failed (") +
-          (info.status == HDD_SOLVE_MAX_ITER ? "max_iter reached" : "breakdown: the matrix is not positive definite?") +
-          ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) +
-          " iterations, residual " + std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm));
+    if (info.status != HDD_SOLVE_CONVERGED) throw Stuff::Exceptions::linear_solver_failed(solver_failed(info, ""));
     return info;
   }
   std::vector<double> apply_inverse(const std::vector<double>& b, double mu = 0.0, const SolverOptions& options = SolverOptions(),
@@ -762,9 +755,7 @@ class AffinelyDecomposedMatrix {
     operands(mu, v, theta);
     const hdd_csr pat = pattern->csr();
     const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
-    hdd_solve_options opt{options.rtol, options.atol, options.max_iter, options.check_every, options.precond,
-                          options.block_size, x0 ? HDD_SOLVE_X0 : 0, 0};
-    if (opt.block_size == 0 && !tile_nbrs) opt.block_size = 1;
+    const hdd_solve_options opt = solve_options(options, x0);
     const int64_t n_work = std::max<int64_t>(hdd_operator_solve_batched_workspace(rows, opt.block_size, n_rhs), 1);
     internal::DeviceArray<double> work{size_t(n_work)};
     std::vector<hdd_solve_info> infos(size_t(n_rhs), hdd_solve_info{});
@@ -772,16 +763,10 @@ class AffinelyDecomposedMatrix {
                                                theta.data(), range, d_b, ldb, d_x, ldx, n_rhs, &opt, work.get(), n_work,
                                                nullptr, 0, infos.data(), stream),
                     "hdd_operator_solve_batched");
-    for (int32_t j = 0; j < n_rhs; ++j) {
-      const hdd_solve_info& info = infos[size_t(j)];
-      if (info.status != HDD_SOLVE_CONVERGED)
+    for (int32_t j = 0; j < n_rhs; ++j)
+      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
         throw Stuff::Exceptions::linear_solver_failed(
-            std::string("apply_inverse: linear solver failed for right-hand side ") + std::to_string(j) + " of " +
-            std::to_string(n_rhs) + " (" +
-            (info.status == HDD_SOLVE_MAX_ITER ? "max_iter reached" : "breakdown: the matrix is not positive definite?") +
-            ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) +
-            " iterations, residual " + std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm));
-    }
+            solver_failed(infos[size_t(j)], " for right-hand side " + std::to_string(j) + " of " + std::to_string(n_rhs)));
     return infos;
   }
   std::vector<std::vector<double>> apply_inverse(const std::vector<std::vector<double>>& b, double mu = 0.0,
@@ -826,6 +811,20 @@ class AffinelyDecomposedMatrix {
     for (size_t q = 0; q < comps.size(); ++q) { v.push_back(comps[q]->get()); theta.push_back(coefficients[q].evaluate(mu)); }
     if (v.empty() || v.size() > HDD_MAX_COMP)
       throw Stuff::Exceptions::wrong_input_given("apply: 1..HDD_MAX_COMP value arrays expected");
+  }
+  // the ABI's options of both apply_inverse: without the mesh's neighbours block_size 0 is the point Jacobi
+  hdd_solve_options solve_options(const Discretizations::SolverOptions& o, bool x0) const
+  {
+    return hdd_solve_options{o.rtol, o.atol, o.max_iter, o.check_every, o.precond, o.block_size == 0 && !tile_nbrs ? 1 : o.block_size,
+                             x0 ? HDD_SOLVE_X0 : 0, 0};
+  }
+  // the message of linear_solver_failed; which: "" or " for right-hand side j of n"
+  static std::string solver_failed(const hdd_solve_info& info, const std::string& which)
+  {
+    return "apply_inverse: linear solver failed" + which + " (" +
+           (info.status == HDD_SOLVE_MAX_ITER ? "max_iter reached" : "breakdown: the matrix is not positive definite?") +
+           ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) + " iterations, residual " +
+           std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm);
   }
   std::vector<double> trimmed(const internal::DeviceArray<double>& a) const
   {
