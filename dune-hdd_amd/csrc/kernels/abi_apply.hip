@@ -140,7 +140,91 @@ int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const doubl
   return HDD_OK;
 }
 
+int hdd::abi::plan_apply_multi(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P)
+{
+  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, P)) return rc;
+  if (P.tile && !apply_multi_tile_fits(P.nb, n_comp)) {
+    if (!pattern->row_ptr || !pattern->col) return fail(HDD_ERR_INVALID, who, "pattern without row_ptr / col (component images beyond the LDS)");
+    P.tile = false;
+    P.short_rows = pattern->n_rows == 0 || pattern->nnz / std::max<int64_t>(pattern->n_rows, 1) <= 32;
+  }
+  return HDD_OK;
+}
+
+void hdd::abi::apply_multi_thetas(dev::ApplyMultiArgs& ma, const double* theta, int64_t ldt, int v0)
+{
+  for (int v = 0; v < dev::APPLY_NV; ++v) {
+    const int64_t j = v0 + (v < ma.a.nv ? v : 0);
+    for (int q = 0; q < HDD_MAX_COMP; ++q) ma.theta[v][q] = q < ma.a.n_comp ? (theta ? theta[j * ldt + q] : 1.0) : 0.0;
+  }
+}
+
+namespace {
+template <int NB, int NF, int NC>
+hipError_t launch_tile_multi(const hdd_ctx* ctx, const dev::ApplyMultiArgs& ma, hipStream_t s)
+{
+  using I = dev::ApplyImage<NB, NF>;
+  static_assert(NC * I::BYTES <= 64 * 1024, "the dynamic LDS a launch gets without raising the kernel's attribute");
+  const int64_t n_tiles = (ma.a.e_end - ma.a.e_begin + 63) / 64;
+  const int64_t G = hdd::abi::apply_tile_grid<NB, NF>(ctx, n_tiles);
+  last_apply_kernel_slot() = NB == 3 ? "apply_tile_multi_kernel<3, 3, 4>" : "apply_tile_multi_kernel<4, 4, 4>";
+  hipLaunchKernelGGL((dev::apply_tile_multi_kernel<NB, NF, dev::APPLY_NV, false, NC>), dim3(unsigned(G)), dim3(64), NC * I::BYTES, s, ma, n_tiles);
+  return hipGetLastError();
+}
+
+template <int G>
+hipError_t launch_csr_multi(const dev::ApplyMultiArgs& ma, hipStream_t s)
+{
+  const unsigned grid = unsigned(hdd::abi::apply_csr_grid<G>(ma.a.row_end - ma.a.row_begin));
+  last_apply_kernel_slot() = G == 8 ? "apply_csr_multi_kernel<8, 4>" : "apply_csr_multi_kernel<64, 4>";
+  hipLaunchKernelGGL((dev::apply_csr_multi_kernel<G, dev::APPLY_NV>), dim3(grid), dim3(256), 0, s, ma);
+  return hipGetLastError();
+}
+}  // namespace
+
+int hdd::abi::run_apply_multi(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* theta, int64_t ldt, const double* d_x, int64_t ldx,
+                              double* d_y, int64_t ldy, int32_t n_vec, void* stream)
+{
+  if (P.a.row_end == P.a.row_begin) return HDD_OK;
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, who);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  for (int v0 = 0; v0 < n_vec; v0 += dev::APPLY_NV) {
+    dev::ApplyMultiArgs ma;
+    dev::ApplyArgs& a = ma.a;
+    a = P.a;
+    a.nv = std::min<int>(dev::APPLY_NV, n_vec - v0);
+    a.x = d_x + int64_t(v0) * ldx;
+    a.ldx = ldx;
+    a.y = d_y + int64_t(v0) * ldy;
+    a.ldy = ldy;
+    apply_multi_thetas(ma, theta, ldt, v0);
+    if (P.tile && P.nb == 3)
+      e = a.n_comp == 1 ? launch_tile_multi<3, 3, 1>(ctx, ma, s) : a.n_comp == 2 ? launch_tile_multi<3, 3, 2>(ctx, ma, s) : launch_tile_multi<3, 3, 3>(ctx, ma, s);
+    else if (P.tile) e = launch_tile_multi<4, 4, 1>(ctx, ma, s);
+    else e = P.short_rows ? launch_csr_multi<8>(ma, s) : launch_csr_multi<64>(ma, s);
+    if (e != hipSuccess) return hip_fail(e, who);
+  }
+  return HDD_OK;
+}
+
 extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot(); }
+
+extern "C" int hdd_operator_apply_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                                        int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range,
+                                        const double* d_x, int64_t ldx, double* d_y, int64_t ldy, int32_t n_vec, void* stream)
+{
+  const char* who = "hdd_operator_apply_multi";
+  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_vec < 1 || n_vec > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_vec outside 1..HDD_MAX_VEC");
+  ApplyPlan P;
+  if (int rc = hdd::abi::plan_apply_multi(who, ctx, mesh, pattern, d_vals, n_comp, nullptr, range, P)) return rc;
+  if (theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
+  if (ldx < P.a.col_end - P.a.col_begin || ldy < P.a.row_end - P.a.row_begin)
+    return fail(HDD_ERR_INVALID, who, "ldx / ldy smaller than the range");
+  return hdd::abi::run_apply_multi(who, ctx, P, theta, ldt, d_x, ldx, d_y, ldy, n_vec, stream);
+}
 
 extern "C" int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,
                                   const double* const* d_vals, int32_t n_comp, const double* theta,

@@ -3,7 +3,9 @@
 // apply_inverse of ContainerBasedDefault::uncached_solve (base.hh:327-367) on the device, and
 // hdd_operator_solve_batched, the same iteration for up to HDD_MAX_VEC right-hand sides in groups of APPLY_NV.  The
 // operator arguments are checked and dispatched by plan_apply (apply_plan.hh), as hdd_operator_apply's.
-// One driver serves both entries: checked (every argument check), Solve (the workspace and its two views), setup,
+// hdd_operator_solve_multi is the batched solve with a theta per column: the multi-theta applies and every column's
+// own inverse blocks.
+// One driver serves the entries: checked (every argument check), Solve (the workspace and its two views), setup,
 // iterate (enqueue and look) and finish; an entry adds its own init-state kernel and its launches of one iteration.
 #include <hip/hip_runtime.h>
 
@@ -24,16 +26,19 @@ namespace dev = hdd::dev;
 namespace {
 constexpr int NVB = dev::APPLY_NV;
 
-// what differs between the two entries before the iteration: the names in the messages, the head of the workspace
-// (doubles before the partial sums) and who gives the leading dimensions
+// what differs between the entries before the iteration: the names in the messages, the head of the workspace
+// (doubles before the partial sums), who gives the leading dimensions and whether every column has a theta, and
+// with it inverse blocks, of its own
 struct Entry {
   const char *who, *workspace;
   int64_t head;
   bool dense;   // one column: ldb = ldx = rows, ldh = max_iter + 1 whatever the caller passed
+  bool own;     // theta is [n_rhs][ldt]
 };
-constexpr Entry SINGLE{"hdd_operator_solve", "hdd_operator_solve_workspace", int64_t(sizeof(dev::SolveState) / 8), true};
+constexpr Entry SINGLE{"hdd_operator_solve", "hdd_operator_solve_workspace", int64_t(sizeof(dev::SolveState) / 8), true, false};
 // states of HDD_MAX_VEC columns, then the group words
-constexpr Entry BATCHED{"hdd_operator_solve_batched", "hdd_operator_solve_batched_workspace", int64_t(hdd_ctx::SOLVE_STATE_BYTES / 8), false};
+constexpr Entry BATCHED{"hdd_operator_solve_batched", "hdd_operator_solve_batched_workspace", int64_t(hdd_ctx::SOLVE_STATE_BYTES / 8), false, false};
+constexpr Entry MULTI{"hdd_operator_solve_multi", "hdd_operator_solve_multi_workspace", int64_t(hdd_ctx::SOLVE_STATE_BYTES / 8), false, true};
 
 std::string& last_solve_kernels_slot()
 {
@@ -56,17 +61,18 @@ int64_t even(int64_t n) { return n + (n & 1); }
 int64_t packed(int bs) { return int64_t(bs) * (bs + 1) / 2; }
 
 // head, four kinds of partial sums [column][SOLVE_PARTS], p q r z [column][even(rows)] (each column starting 16-byte
-// aligned), the packed inverse blocks once: Solve::carve
-int64_t workspace_doubles(int64_t rows, int bs, int n_rhs, int64_t head)
+// aligned), the packed inverse blocks once -- a theta per column: once per column: Solve::carve
+int64_t blocks_doubles(int64_t rows, int bs) { return even(rows / bs * packed(bs)); }
+int64_t workspace_doubles(int64_t rows, int bs, int n_rhs, const Entry& E)
 {
-  return head + int64_t(n_rhs) * (4 * int64_t(dev::SOLVE_PARTS) + 4 * even(rows)) + even(rows / bs * packed(bs));
+  return E.head + int64_t(n_rhs) * (4 * int64_t(dev::SOLVE_PARTS) + 4 * even(rows)) + (E.own ? n_rhs : 1) * blocks_doubles(rows, bs);
 }
 
 // block_size 0 (the mesh's nb, unknown here): enough for every block size
-int64_t workspace_any(int64_t rows, int block_size, int n_rhs, int64_t head)
+int64_t workspace_any(int64_t rows, int block_size, int n_rhs, const Entry& E)
 {
   int64_t w = 0;
-  for (int bs = block_size ? block_size : 1; bs <= (block_size ? block_size : 8); ++bs) w = std::max(w, workspace_doubles(rows, bs, n_rhs, head));
+  for (int bs = block_size ? block_size : 1; bs <= (block_size ? block_size : 8); ++bs) w = std::max(w, workspace_doubles(rows, bs, n_rhs, E));
   return w;
 }
 
@@ -85,6 +91,10 @@ struct Solve {
   dev::SolveState* state;   // [n_rhs]
   int32_t* stop;            // [groups] (batch)
   double *part_pq, *part_rz, *part_rr, *part_bb, *p, *q, *r, *z, *dinv, *x, *history;
+  // a theta per column (hdd_operator_solve_multi): the caller's [n_rhs][ldt] (NULL: ones), column c's inverse blocks
+  // at dinv + c * ld_dinv, its partial counts of indefinite blocks at part_pq + c * bad_stride; else zeros
+  const double* thetas;
+  int64_t ldt, ld_dinv, bad_stride;
 
   void carve(double* w, int64_t head)
   {
@@ -99,7 +109,7 @@ struct Solve {
   // column c alone: the setup kernels of both entries and the single solve's iteration
   dev::SolveVectors column(int c) const
   {
-    return dev::SolveVectors{state + c, x + c * ldx, p + c * ldw, q + c * ldw, r + c * ldw, z + c * ldw, dinv,
+    return dev::SolveVectors{state + c, x + c * ldx, p + c * ldw, q + c * ldw, r + c * ldw, z + c * ldw, dinv + c * ld_dinv,
                              part_pq + int64_t(c) * n_pq, part_rz + c * n_parts, part_rr + c * n_parts, part_bb + c * n_parts,
                              rows, n_pq, history ? history + c * ldh : nullptr};
   }
@@ -107,8 +117,8 @@ struct Solve {
   dev::SolveBatch group(int g0) const
   {
     const dev::SolveVectors v = column(g0);
-    return dev::SolveBatch{v.state, stop + g0 / NVB, v.x, ldx, v.p, v.q, v.r, v.z, ldw, dinv, v.part_pq, v.part_rz, v.part_rr,
-                           rows, n_pq, std::min(NVB, n_rhs - g0), v.history, ldh};
+    return dev::SolveBatch{v.state, stop + g0 / NVB, v.x, ldx, v.p, v.q, v.r, v.z, ldw, v.dinv, v.part_pq, v.part_rz, v.part_rr,
+                           rows, n_pq, std::min(NVB, n_rhs - g0), v.history, ldh, ld_dinv};
   }
 };
 
@@ -127,17 +137,21 @@ int64_t dot_grid(const hdd_ctx* ctx, const ApplyPlan& P)
   return G;
 }
 
-// Every argument check of both entries, in the order of their messages, without a device call; fills S except its
+// Every argument check of the entries, in the order of their messages, without a device call; fills S except its
 // workspace pointers.  The single solve has n_rhs = 1 and dense leading dimensions, so the batch's checks pass.
+// theta is [n_comp], with E.own [n_rhs][ldt].
 int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals, int32_t n_comp,
-            const double* theta, const hdd_block_range* range, const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs,
+            const double* theta, int64_t ldt, const hdd_block_range* range, const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs,
             const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
             void* stream, Solve& S)
 {
   const char* who = E.who;
   if (!d_b || !d_x || !opt || !d_work || !info) return fail(HDD_ERR_INVALID, who, "null argument");
   if (n_rhs < 1 || n_rhs > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_rhs outside 1..HDD_MAX_VEC");
-  if (int rc = hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, S.P)) return rc;
+  if (int rc = E.own ? hdd::abi::plan_apply_multi(who, ctx, mesh, pattern, d_vals, n_comp, nullptr, range, S.P)
+                     : hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, S.P))
+    return rc;
+  if (E.own && theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
   const dev::ApplyArgs& a = S.P.a;
   if (a.row_begin != a.col_begin || a.row_end != a.col_end)
     return fail(HDD_ERR_INVALID, who, "the whole (square) matrix or a square diagonal range expected");
@@ -161,7 +175,7 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   if (E.dense) ldb = ldx = rows, ldh = int64_t(opt->max_iter) + 1;
   if (ldb < rows || ldx < rows) return fail(HDD_ERR_INVALID, who, "ldb / ldx smaller than the range");
   if (d_history && ldh < int64_t(opt->max_iter) + 1) return fail(HDD_ERR_INVALID, who, "ldh smaller than max_iter + 1");
-  if (n_work < workspace_doubles(rows, bs, n_rhs, E.head))
+  if (n_work < workspace_doubles(rows, bs, n_rhs, E))
     return fail(HDD_ERR_INVALID, who, (std::string("n_work smaller than ") + E.workspace).c_str());
   S.bs = bs;
   S.n_rhs = n_rhs;
@@ -181,6 +195,10 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   S.s = static_cast<hipStream_t>(stream);
   S.x = d_x;
   S.history = d_history;
+  S.thetas = E.own ? theta : nullptr;
+  S.ldt = ldt;
+  S.ld_dinv = E.own ? blocks_doubles(rows, bs) : 0;
+  S.bad_stride = E.own ? dev::SOLVE_PARTS : 0;
   // the 16-byte paths need every column of x aligned
   S.a16 = reinterpret_cast<uintptr_t>(d_work) % 16 == 0 && reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && (n_rhs == 1 || ldx % 2 == 0);
   S.carve(d_work, E.head);
@@ -237,36 +255,79 @@ hipError_t launch_apply_dot(const Solve& S, const double* p, double* q, int nv, 
   return hipGetLastError();
 }
 
-// names of the iteration's kernels; the batch's vector count is the instantiation's (APPLY_NV), not n_rhs
-void name_kernels(const Solve& S, bool batched)
+// launch_apply_dot<APPLY_NV> with a theta per column: the group's columns begin at g0
+template <int NC>
+void launch_tile_dot_multi(const Solve& S, const dev::ApplyMultiArgs& ma, int64_t n_tiles)
 {
-  const std::string nv = std::to_string(batched ? NVB : 1);
-  std::string& nm = last_solve_kernels_slot();
-  if (S.P.tile) nm = S.P.nb == 3 ? "apply_tile_kernel<3, 3, " : "apply_tile_kernel<4, 4, ";
-  else nm = S.P.short_rows ? "apply_csr_kernel<8, " : "apply_csr_kernel<64, ";
-  nm += nv + ", dot> + cg_update<" + std::to_string(S.bs) + (S.pre ? "" : ", none");
-  nm += batched ? ", " + nv + "> + cg_direction<" + nv + ">" : "> + cg_direction";
+  using I = dev::ApplyImage<3, 3>;
+  static_assert(NC * I::BYTES <= 64 * 1024, "the dynamic LDS a launch gets without raising the kernel's attribute");
+  hipLaunchKernelGGL((dev::apply_tile_multi_kernel<3, 3, NVB, true, NC>), grid(S.n_pq), dim3(64), NC * I::BYTES, S.s, ma, n_tiles);
 }
 
-// Setup of both entries: the inverse diagonal blocks once (their counts of indefinite blocks in part_pq, read by
-// the init-state kernel before the first apply overwrites them), r = b - A x0 over all columns, then cg_init_kernel
-// a column at a time on the single solve's grid (same sums).  The entry's init-state kernel follows.
+hipError_t launch_apply_dot_multi(const Solve& S, int g0, const double* p, double* q, int nv, double* part_pq, const int32_t* done_at, int k)
+{
+  dev::ApplyMultiArgs ma;
+  dev::ApplyArgs& a = ma.a;
+  a = S.P.a;
+  a.nv = nv;
+  a.x = p;
+  a.y = q;
+  a.ldx = a.ldy = S.ldw;
+  a.partial = part_pq;
+  a.done_at = done_at;
+  a.iteration = k;
+  hdd::abi::apply_multi_thetas(ma, S.thetas, S.ldt, g0);
+  const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
+  if (S.P.tile && S.P.nb == 3) {
+    if (a.n_comp == 1) launch_tile_dot_multi<1>(S, ma, n_tiles);
+    else if (a.n_comp == 2) launch_tile_dot_multi<2>(S, ma, n_tiles);
+    else launch_tile_dot_multi<3>(S, ma, n_tiles);
+  } else if (S.P.tile)
+    hipLaunchKernelGGL((dev::apply_tile_multi_kernel<4, 4, NVB, true, 1>), grid(S.n_pq), dim3(64), (dev::ApplyImage<4, 4>::BYTES), S.s, ma, n_tiles);
+  else if (S.P.short_rows)
+    hipLaunchKernelGGL((dev::apply_csr_multi_kernel<8, NVB, true>), grid(S.n_pq), dim3(256), 0, S.s, ma);
+  else
+    hipLaunchKernelGGL((dev::apply_csr_multi_kernel<64, NVB, true>), grid(S.n_pq), dim3(256), 0, S.s, ma);
+  return hipGetLastError();
+}
+
+// names of the iteration's kernels; the batch's vector count is the instantiation's (APPLY_NV), not n_rhs
+void name_kernels(const Entry& E, const Solve& S)
+{
+  const bool batched = !E.dense;
+  const std::string nv = std::to_string(batched ? NVB : 1), multi = E.own ? "multi_" : "";
+  std::string& nm = last_solve_kernels_slot();
+  if (S.P.tile) nm = "apply_tile_" + multi + (S.P.nb == 3 ? "kernel<3, 3, " : "kernel<4, 4, ");
+  else nm = "apply_csr_" + multi + (S.P.short_rows ? "kernel<8, " : "kernel<64, ");
+  nm += nv + ", dot> + cg_update<" + std::to_string(S.bs) + (S.pre ? "" : ", none");
+  nm += batched ? ", " + nv + (E.own && S.pre ? ", own" : "") + "> + cg_direction<" + nv + ">" : "> + cg_direction";
+}
+
+// Setup of the entries: the inverse diagonal blocks once (their counts of indefinite blocks in part_pq, read by
+// the init-state kernel before the first apply overwrites them) -- with a theta per column once per column, at
+// theta_c, into the column's slice --, r = b - A x0 over all columns, then cg_init_kernel a column at a time on the
+// single solve's grid (same sums).  The entry's init-state kernel follows.
 int setup(const Entry& E, hdd_ctx* ctx, Solve& S, const double* d_b)
 {
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_fail(e, E.who);
-  name_kernels(S, !E.dense);
-  if (S.pre) {
+  name_kernels(E, S);
+  for (int c = 0; S.pre && c < (E.own ? S.n_rhs : 1); ++c) {
+    dev::ApplyArgs a = S.P.a;
+    for (int q = 0; E.own && q < a.n_comp; ++q) a.theta[q] = S.thetas ? S.thetas[c * S.ldt + q] : 1.0;
+    double *dinv = S.dinv + c * S.ld_dinv, *part_bad = S.part_pq + c * S.bad_stride;
     e = with_block(S, [&](auto BS, auto, auto) {
-      if (!S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_csr_kernel<BS()>), grid(S.n_parts), dim3(256), 0, S.s, S.P.a, S.dinv, S.part_pq);
+      if (!S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_csr_kernel<BS()>), grid(S.n_parts), dim3(256), 0, S.s, a, dinv, part_bad);
       if constexpr (BS() == 3 || BS() == 4)
-        if (S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_tile_kernel<BS(), BS()>), grid(S.n_parts), dim3(256), 0, S.s, S.P.a, S.dinv, S.part_pq);
+        if (S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_tile_kernel<BS(), BS()>), grid(S.n_parts), dim3(256), 0, S.s, a, dinv, part_bad);
       return hipGetLastError();
     });
     if (e != hipSuccess) return hip_fail(e, E.who);
   }
   if (S.x0)
-    if (int rc = hdd::abi::run_apply(E.who, ctx, S.P, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s)) return rc;
+    if (int rc = E.own ? hdd::abi::run_apply_multi(E.who, ctx, S.P, S.thetas, S.ldt, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s)
+                       : hdd::abi::run_apply(E.who, ctx, S.P, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s))
+      return rc;
   for (int c = 0; c < S.n_rhs; ++c) {
     e = with_block(S, [&](auto BS, auto PRE, auto A16) {
       hipLaunchKernelGGL((dev::cg_init_kernel<BS(), PRE(), A16()>), grid(S.n_parts), dim3(256), 0, S.s, S.column(c), d_b + c * S.ldb, S.x0);
@@ -323,13 +384,19 @@ extern "C" const char* hdd_last_solve_kernels(void) { return last_solve_kernels_
 extern "C" int64_t hdd_operator_solve_workspace(int64_t rows, int32_t block_size)
 {
   if (rows < 0 || block_size < 0 || block_size > 8) return 0;
-  return workspace_any(rows, block_size, 1, SINGLE.head);
+  return workspace_any(rows, block_size, 1, SINGLE);
 }
 
 extern "C" int64_t hdd_operator_solve_batched_workspace(int64_t rows, int32_t block_size, int32_t n_rhs)
 {
   if (rows < 0 || block_size < 0 || block_size > 8 || n_rhs < 1 || n_rhs > HDD_MAX_VEC) return 0;
-  return workspace_any(rows, block_size, n_rhs, BATCHED.head);
+  return workspace_any(rows, block_size, n_rhs, BATCHED);
+}
+
+extern "C" int64_t hdd_operator_solve_multi_workspace(int64_t rows, int32_t block_size, int32_t n_rhs)
+{
+  if (rows < 0 || block_size < 0 || block_size > 8 || n_rhs < 1 || n_rhs > HDD_MAX_VEC) return 0;
+  return workspace_any(rows, block_size, n_rhs, MULTI);
 }
 
 extern "C" int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
@@ -339,7 +406,7 @@ extern "C" int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
 {
   const Entry& E = SINGLE;
   Solve S;
-  if (int rc = checked(E, ctx, mesh, pattern, d_vals, n_comp, theta, range, d_b, 0, d_x, 0, 1, opt, d_work, n_work, d_history, 0, info, stream, S))
+  if (int rc = checked(E, ctx, mesh, pattern, d_vals, n_comp, theta, 0, range, d_b, 0, d_x, 0, 1, opt, d_work, n_work, d_history, 0, info, stream, S))
     return rc;
   if (S.rows == 0) return HDD_OK;
   if (int rc = setup(E, ctx, S, d_b)) return rc;
@@ -364,20 +431,22 @@ extern "C" int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
 
 // Several right-hand sides per call: setup and iteration are those above, per iteration and group of APPLY_NV columns
 // the DOT apply on the single solve's dot grid, cg_update_batched on its update grid, cg_direction_batched.
-extern "C" int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
-                                          int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_b,
-                                          int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs, const hdd_solve_options* opt,
-                                          double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
-                                          void* stream)
+// With E.own (hdd_operator_solve_multi) the applies are the multi-theta ones and cg_update_batched loads column c's own
+// inverse blocks.
+namespace {
+int solve_columns(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                  int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range, const double* d_b,
+                  int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs, const hdd_solve_options* opt,
+                  double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
+                  void* stream)
 {
-  const Entry& E = BATCHED;
   Solve S;
-  if (int rc = checked(E, ctx, mesh, pattern, d_vals, n_comp, theta, range, d_b, ldb, d_x, ldx, n_rhs, opt, d_work, n_work, d_history, ldh, info, stream, S))
+  if (int rc = checked(E, ctx, mesh, pattern, d_vals, n_comp, theta, ldt, range, d_b, ldb, d_x, ldx, n_rhs, opt, d_work, n_work, d_history, ldh, info, stream, S))
     return rc;
   if (S.rows == 0) return HDD_OK;
   if (int rc = setup(E, ctx, S, d_b)) return rc;
   hipLaunchKernelGGL(dev::cg_init_state_batched_kernel, dim3(1), dim3(64), 0, S.s, S.state, S.stop, int(n_rhs), S.part_pq,
-                     S.pre ? int(S.n_parts) : 0, S.part_bb, S.part_rz, S.part_rr, int(S.n_parts), opt->rtol, opt->atol, d_history, ldh);
+                     S.pre ? int(S.n_parts) : 0, S.part_bb, S.part_rz, S.part_rr, int(S.n_parts), opt->rtol, opt->atol, d_history, ldh, S.bad_stride);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return hip_fail(e, E.who);
   int k;
@@ -385,10 +454,11 @@ extern "C" int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, co
     hipError_t e = hipSuccess;
     for (int g0 = 0; g0 < n_rhs && e == hipSuccess; g0 += NVB) {
       const dev::SolveBatch v = S.group(g0);
-      e = launch_apply_dot<NVB>(S, v.p, v.q, v.nv, v.part_pq, v.stop, k);
+      e = E.own ? launch_apply_dot_multi(S, g0, v.p, v.q, v.nv, v.part_pq, v.stop, k) : launch_apply_dot<NVB>(S, v.p, v.q, v.nv, v.part_pq, v.stop, k);
       if (e != hipSuccess) return e;
       e = with_block(S, [&](auto BS, auto PRE, auto A16) {
-        hipLaunchKernelGGL((dev::cg_update_batched_kernel<BS(), PRE(), A16(), NVB>), grid(S.n_parts), dim3(256), 0, S.s, v, k);
+        if (E.own && PRE()) hipLaunchKernelGGL((dev::cg_update_batched_kernel<BS(), PRE(), A16(), NVB, PRE()>), grid(S.n_parts), dim3(256), 0, S.s, v, k);
+        else hipLaunchKernelGGL((dev::cg_update_batched_kernel<BS(), PRE(), A16(), NVB>), grid(S.n_parts), dim3(256), 0, S.s, v, k);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL((dev::cg_direction_batched_kernel<PRE(), NVB>), grid(S.dgrid), dim3(256), 0, S.s, v, k, int(S.n_parts));
@@ -398,4 +468,26 @@ extern "C" int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, co
     return e;
   });
   return rc ? rc : finish(E, ctx, S, k, info);
+}
+}  // namespace
+
+extern "C" int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                                          int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_b,
+                                          int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs, const hdd_solve_options* opt,
+                                          double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
+                                          void* stream)
+{
+  return solve_columns(BATCHED, ctx, mesh, pattern, d_vals, n_comp, theta, 0, range, d_b, ldb, d_x, ldx, n_rhs, opt, d_work, n_work,
+                       d_history, ldh, info, stream);
+}
+
+// A theta per column: the same affine components at n_rhs parameters.
+extern "C" int hdd_operator_solve_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                                        int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range,
+                                        const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs,
+                                        const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history,
+                                        int64_t ldh, hdd_solve_info* info, void* stream)
+{
+  return solve_columns(MULTI, ctx, mesh, pattern, d_vals, n_comp, theta, ldt, range, d_b, ldb, d_x, ldx, n_rhs, opt, d_work, n_work,
+                       d_history, ldh, info, stream);
 }

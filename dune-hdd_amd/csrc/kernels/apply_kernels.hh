@@ -283,6 +283,225 @@ __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
   }
 }
 
+// ---- a theta per vector (hdd_operator_apply_multi, hdd_operator_solve_multi) -------------------------------------
+// y_v = (sum_q theta[v][q] A_q) x_v: the same affine components at several parameters, the value stream read once
+// per group of NV vectors.  Vector v keeps the arithmetic of the single-theta kernels on (theta[v], x_v): the matrix
+// entry m = theta[v][0] a_0, m = fma(theta[v][q], a_q, m) for q = 1 .. n_comp - 1 in separate statements, then
+// acc = fma(m, x, acc) -- so y_v, and the DOT partial sums on the same grid, are bit for bit those of the
+// single-theta launch.  Entries of vectors >= nv are copies of vector 0's (never stored).
+struct ApplyMultiArgs {
+  ApplyArgs a;                         // a.theta is not read
+  double theta[APPLY_NV][HDD_MAX_COMP];
+};
+
+// apply_tile_kernel with NC (= n_comp, compile time) component images in the LDS instead of the one theta-combined
+// image: image q holds component q's values of the tile in ApplyImage's layout (apply_swz) at lds + q * I::BYTES / 8,
+// and the combination happens at the read: per matrix entry NC LDS reads, then per vector the theta chain and one FMA.
+// Tile order, lane -> element, the x gathers, xown / dot, the shuffle trees and the partials are apply_tile_kernel's;
+// it runs on the same grids.  NC * I::BYTES of LDS per wave: P1 19,456 B per image (NC <= 3: 58,368 B, inside the
+// 64 KB a launch gets without raising the kernel's dynamic-LDS attribute), Q1 40,960 B (NC = 1).
+template <int NB, int NF, int NV, bool DOT, int NC>
+__global__ void __launch_bounds__(64) apply_tile_multi_kernel(const ApplyMultiArgs ma, int64_t n_tiles)
+{
+  using I = ApplyImage<NB, NF>;
+  constexpr int CH = I::CHUNKS, U = I::U, IMG = I::BYTES / 8;
+  static_assert(NV <= APPLY_NV && NC >= 1 && NC <= HDD_MAX_COMP, "theta[APPLY_NV][HDD_MAX_COMP]");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  const ApplyArgs& a = ma.a;
+  const int lane = threadIdx.x;
+  [[maybe_unused]] double dot[NV] = {};   // DOT: this lane's x_v . y_v over its elements, in tile order
+  if constexpr (DOT)
+    if (*a.done_at <= a.iteration) return;   // (wave-uniform)
+  const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
+  const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
+  __amdgpu_buffer_rsrc_t xr[NV];
+  double th[NV][NC];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) {
+    xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) th[v][q] = ma.theta[v][q];
+  }
+  for (int64_t t = r.t; t < r.t_end; t += r.t_step) {
+    const int64_t t0 = a.e_begin + t * 64;
+    const int64_t tend = t0 + 64 < a.e_end ? t0 + 64 : a.e_end;
+    const bool active = t0 + lane < tend;
+    const int64_t e = active ? t0 + lane : t0;
+    int nbr[NF];
+#pragma unroll
+    for (int f = 0; f < NF; ++f) nbr[f] = a.nbrs[f * a.n_local + e];
+    const int64_t base = apply_uni64(a.elem_ptr[t0 - a.own_begin]);
+    const int64_t tile_end = apply_uni64(a.elem_ptr[tend - a.own_begin]);
+    const int64_t base_al = base & ~int64_t(1);
+    const int tlen_al = int(tile_end - base_al);   // image length in values, from the aligned origin
+    // the previous tile's images have been read by every lane
+    lds_wave_sync();
+    // [stream the tile's values, a component at a time -> its LDS image]; chunks beyond the tile read zero
+    const uint32_t vbytes = tile_end > base_al ? uint32_t(tlen_al) * 8u : 0u;
+#pragma unroll
+    for (int q = 0; q < NC; ++q) {
+      const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
+#pragma unroll 1
+      for (int k0 = 0; k0 < CH; k0 += U) {
+        if (k0 * 128 >= tlen_al) break;
+        dvec2 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) v[u] = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
+#pragma unroll
+        for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + q * IMG + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
+      }
+      // an odd image length: the last value has no whole 16-byte chunk inside the tile's range
+      if ((tlen_al & 1) && lane == 0) lds[q * IMG + apply_swz(tlen_al - 1)] = ld64f(vr, uint32_t(tlen_al - 1) * 8u);
+    }
+    lds_wave_sync();
+    // [lane = element: row block from the images, block columns from the neighbours, x gathered per block]
+    int nint = 0;
+#pragma unroll
+    for (int f = 0; f < NF; ++f) nint += nbr[f] >= 0;
+    const int off = tile_offset<NB>(nint, active) + int(base - base_al);
+    if (!active) continue;
+    int id[NF + 1];
+    id[0] = int(e);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) id[f + 1] = nbr[f] >= 0 ? nbr[f] : 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < NF; ++i)
+#pragma unroll
+      for (int j = 0; j < NF - i; ++j) {
+        const int lo = id[j] < id[j + 1] ? id[j] : id[j + 1], hi = id[j] < id[j + 1] ? id[j + 1] : id[j];
+        id[j] = lo;
+        id[j + 1] = hi;
+      }
+    const int rl = NB * (nint + 1);   // row length
+    double acc[NV][NB];
+    [[maybe_unused]] double xown[NV][NB] = {};
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) acc[v][i] = 0.0;
+#pragma unroll
+    for (int b = 0; b <= NF; ++b) {
+      if (b > nint || id[b] < a.ce_begin || id[b] >= a.ce_end) continue;   // skipped, not multiplied by zero
+      const uint32_t xo = uint32_t(id[b] - int(a.ce_begin)) * uint32_t(NB * 8);
+      double xv[NV][NB];
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) xv[v][j] = v < a.nv ? ld64f(xr[v], xo + 8u * j) : 0.0;
+      if constexpr (DOT)   // the element's own block is one of the gathered ones: these are its rows of x
+        if (id[b] == int(e))
+#pragma unroll
+          for (int v = 0; v < NV; ++v)
+#pragma unroll
+            for (int j = 0; j < NB; ++j) xown[v][j] = xv[v][j];
+#pragma unroll
+      for (int i = 0; i < NB; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+          const int p = apply_swz(off + i * rl + b * NB + j);
+          double c[NC];
+#pragma unroll
+          for (int q = 0; q < NC; ++q) c[q] = lds[q * IMG + p];
+#pragma unroll
+          for (int v = 0; v < NV; ++v) {
+            double m = th[v][0] * c[0];
+#pragma unroll
+            for (int q = 1; q < NC; ++q) m = __builtin_fma(th[v][q], c[q], m);
+            acc[v][i] = __builtin_fma(m, xv[v][j], acc[v][i]);
+          }
+        }
+    }
+    double* yo = a.y + (e - a.e_begin) * NB;
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+      if (v < a.nv)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) yo[v * a.ldy + i] = acc[v][i];
+    if constexpr (DOT)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) dot[v] = __builtin_fma(xown[v][i], acc[v][i], dot[v]);
+  }
+  if constexpr (DOT) {   // every lane is back here, whatever its tiles were
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      if (lane == 0 && v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = dot[v];
+    }
+  }
+}
+
+// apply_csr_kernel with the theta chain per vector and nonzero: the n_comp values are loaded once, then NV chains.
+// Row -> group, shuffle order and partials are apply_csr_kernel's; every n_comp <= HDD_MAX_COMP.
+template <int G, int NV, bool DOT = false>
+__global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiArgs ma)
+{
+  static_assert(NV <= APPLY_NV, "theta[APPLY_NV][HDD_MAX_COMP]");
+  const ApplyArgs& a = ma.a;
+  [[maybe_unused]] double dot[NV] = {};   // DOT: the group leaders' x_r y_r over their rows, in row order
+  if constexpr (DOT)
+    if (*a.done_at <= a.iteration) return;   // (uniform)
+  const int gl = threadIdx.x % G;
+  const int64_t n_rows = a.row_end - a.row_begin;
+  const int64_t stride = int64_t(gridDim.x) * (256 / G);
+  for (int64_t rr = int64_t(blockIdx.x) * (256 / G) + threadIdx.x / G; rr < n_rows; rr += stride) {
+    int64_t k0 = a.row_ptr[a.row_begin + rr], k1 = a.row_ptr[a.row_begin + rr + 1];
+    k0 = k0 < 0 ? 0 : k0;
+    k1 = k1 > a.nnz ? a.nnz : k1;
+    double acc[NV];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
+    for (int64_t k = k0 + gl; k < k1; k += G) {
+      const int64_t c = a.col[k];
+      if (c < a.col_begin || c >= a.col_end) continue;   // skipped, not multiplied by zero
+      double m[NV];
+      {
+        const double w = a.vals[0][k];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) m[v] = ma.theta[v][0] * w;
+      }
+      for (int q = 1; q < a.n_comp; ++q) {
+        const double w = a.vals[q][k];
+#pragma unroll
+        for (int v = 0; v < NV; ++v) m[v] = __builtin_fma(ma.theta[v][q], w, m[v]);
+      }
+      const double* xc = a.x + (c - a.col_begin);
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) acc[v] = __builtin_fma(m[v], xc[v * a.ldx], acc[v]);
+    }
+#pragma unroll
+    for (int v = 0; v < NV; ++v)
+#pragma unroll
+      for (int s = G / 2; s > 0; s >>= 1) acc[v] += __shfl_xor(acc[v], s, G);
+    if (gl == 0)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
+    if constexpr (DOT)
+      if (gl == 0)   // square diagonal range: row rr is column rr
+#pragma unroll
+        for (int v = 0; v < NV; ++v)
+          if (v < a.nv) dot[v] = __builtin_fma(a.x[v * a.ldx + rr], acc[v], dot[v]);
+  }
+  if constexpr (DOT) {
+    __shared__ double red[NV][4];
+#pragma unroll
+    for (int v = 0; v < NV; ++v) {
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      if ((threadIdx.x & 63) == 0) red[v][threadIdx.x >> 6] = dot[v];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+#pragma unroll
+      for (int v = 0; v < NV; ++v)
+        if (v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
+  }
+}
+
 // apply2, stage 1: partial[block][i * HDD_MAX_VEC + j] = sum over the block's rows of v_i[r] w_j[r] (fixed row ->
 // thread assignment, shuffle tree, then the four waves in order)
 [[maybe_unused]] static __global__ void __launch_bounds__(256) apply2_partial_kernel(const double* v, int64_t ldv, int n_v, const double* w,

@@ -28,6 +28,21 @@ int plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_cs
 int run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
               int32_t n_vec, void* stream);
 
+// A theta per vector (hdd_operator_apply_multi / _solve_multi): the plan of (theta row 0 or ones), then the tile path
+// only where the n_comp component images fit the LDS a launch gets by default (P1: n_comp <= 3, Q1: n_comp == 1);
+// what does not fit takes the CSR kernel, whose arrays the pattern must then have.
+int plan_apply_multi(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                     int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P);
+inline bool apply_multi_tile_fits(int nb, int n_comp) { return nb == 3 ? n_comp <= 3 : n_comp == 1; }
+
+// the kernel arguments of one group: vector v < nv gets theta[(v0 + v) * ldt + q] (theta NULL: ones), the others
+// copies of the group's first
+void apply_multi_thetas(dev::ApplyMultiArgs& ma, const double* theta, int64_t ldt, int v0);
+
+// the launches of a checked multi plan, the values read once per group of APPLY_NV vectors
+int run_apply_multi(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* theta, int64_t ldt, const double* d_x, int64_t ldx,
+                    double* d_y, int64_t ldy, int32_t n_vec, void* stream);
+
 // workgroups of the tile kernel: as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB); tile_range wants
 // a multiple of 8 workgroups
 template <int NB, int NF>

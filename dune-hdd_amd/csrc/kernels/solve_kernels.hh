@@ -445,27 +445,31 @@ struct SolveBatch {
   int64_t ldx;
   double *p, *q, *r, *z;                // [c * ldw + row]; z == r without a preconditioner
   int64_t ldw;
-  const double* dinv;                   // shared by all columns
+  const double* dinv;                   // shared by all columns; OWN_BLOCKS: column c's blocks at dinv + c * ld_dinv
   double *part_pq, *part_rz, *part_rr;  // [c * n_pq + workgroup], [c * n_parts + workgroup]
   int64_t n;                            // rows
   int32_t n_pq, nv;
   double* history;                      // nullable, history[c * ldh + k]
   int64_t ldh;
+  int64_t ld_dinv;                      // OWN_BLOCKS (a theta per column, hdd_operator_solve_multi) only
 };
 
 // Setup, one wave: the states of all n_rhs columns before the first iteration (cg_init_state_kernel's sums and
-// solve_init_column per column; the partial sums are [column][n_parts]), then the stop words of the groups of APPLY_NV
+// solve_init_column per column; the partial sums are [column][n_parts]), then the stop words of the groups of APPLY_NV.
+// bad_stride 0: one count of indefinite blocks for all columns (one theta); else column c's own inverse blocks left
+// its partial counts at part_bad + c * bad_stride, and a block that is indefinite at theta_c breaks only column c down
 __global__ void __launch_bounds__(64) cg_init_state_batched_kernel(SolveState* state, int32_t* stop, int n_rhs, const double* part_bad,
                                                                    int n_bad, const double* part_bb, const double* part_rz,
                                                                    const double* part_rr, int n_parts, double rtol, double atol,
-                                                                   double* history, int64_t ldh)
+                                                                   double* history, int64_t ldh, int64_t bad_stride)
 {
-  const double bad = solve_wave_sum(part_bad, n_bad);
+  const double bad_all = solve_wave_sum(part_bad, n_bad);
   unsigned live = 0;   // (lane 0) bit c: column c iterates
   for (int c = 0; c < n_rhs; ++c) {
     const double bb = solve_wave_sum(part_bb + int64_t(c) * n_parts, n_parts);
     const double rz = solve_wave_sum(part_rz + int64_t(c) * n_parts, n_parts);
     const double rr = solve_wave_sum(part_rr + int64_t(c) * n_parts, n_parts);
+    const double bad = bad_stride ? solve_wave_sum(part_bad + c * bad_stride, n_bad) : bad_all;
     if (threadIdx.x != 0) continue;
     if (solve_init_column(state[c], history ? history + int64_t(c) * ldh : nullptr, bad, bb, rz, rr, rtol, atol) != 0) live |= 1u << c;
   }
@@ -474,9 +478,10 @@ __global__ void __launch_bounds__(64) cg_init_state_batched_kernel(SolveState* s
 }
 
 // cg_update_kernel for a group: the grid and the lane -> block mapping are the single solve's; the lane loads its
-// packed inverse block once and uses it for every live column.  The per-column accumulators are indexed at compile
-// time (unrolled over NV, guarded), so they stay in registers.
-template <int BS, bool PRE, bool A16, int NV>
+// packed inverse block once and uses it for every live column -- with OWN_BLOCKS (a theta per column) column c's own
+// block inside the column loop instead.  The per-column accumulators are indexed at compile time (unrolled over NV,
+// guarded), so they stay in registers.
+template <int BS, bool PRE, bool A16, int NV, bool OWN_BLOCKS = false>
 __global__ void __launch_bounds__(256) cg_update_batched_kernel(const SolveBatch v, int k)
 {
   __shared__ double red[NV][2][4];
@@ -504,10 +509,11 @@ __global__ void __launch_bounds__(256) cg_update_batched_kernel(const SolveBatch
   for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
     const int64_t o = i * BS;
     [[maybe_unused]] double m[solve_packed<BS>()];
-    if constexpr (PRE) solve_load_packed<BS>(v.dinv + i * solve_packed<BS>(), m);
+    if constexpr (PRE && !OWN_BLOCKS) solve_load_packed<BS>(v.dinv + i * solve_packed<BS>(), m);
 #pragma unroll
     for (int c = 0; c < NV; ++c) {
       if (!live[c]) continue;
+      if constexpr (PRE && OWN_BLOCKS) solve_load_packed<BS>(v.dinv + c * v.ld_dinv + i * solve_packed<BS>(), m);
       const int64_t ow = c * v.ldw + o, ox = c * v.ldx + o;
       solve_update_block<BS, PRE, A16>(v.p + ow, v.q + ow, v.x + ox, v.r + ow, v.z + ow, m, alpha[c], rz[c], rr[c]);
     }

@@ -243,6 +243,10 @@ def lib():
         "hdd_operator_solve_batched_workspace": (_I64, [_I64, _I32, _I32]),
         "hdd_operator_solve_batched": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _VP, _I64,
                                               _VP, _I64, _VP, _VP]),
+        "hdd_operator_apply_multi": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _I32, _VP]),
+        "hdd_operator_solve_multi_workspace": (_I64, [_I64, _I32, _I32]),
+        "hdd_operator_solve_multi": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _VP,
+                                            _I64, _VP, _I64, _VP, _VP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1028,6 +1032,73 @@ def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0
     _check(lib().hdd_operator_solve_batched(ctx.h, *operator, B.data_ptr(), ldb, X.data_ptr(), max(rows, 1), n_rhs,
                                             C.addressof(opt), work.data_ptr(), n_work, None if hist is None else hist.data_ptr(),
                                             ldh, C.addressof(infos), s), "hdd_operator_solve_batched")
+    out = []
+    for j in range(n_rhs):
+        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
+        i.history = None if hist is None else hist[j, :i.iterations + 1]
+        out.append(i)
+    return X, out
+
+
+def _thetas(who, thetas, n, n_comp):
+    """thetas [n, n_comp] (or [n] with one component) as a contiguous host array, None -> None (all ones)"""
+    if thetas is None:
+        return None
+    th = np.ascontiguousarray(thetas, np.float64)
+    if th.ndim == 1 and n_comp == 1:
+        th = th.reshape(-1, 1)
+    if th.shape != (n, n_comp):
+        raise HddError("%s: thetas must be [%d, %d], a row per column" % (who, n, n_comp))
+    return th
+
+
+def apply_multi(ctx, dpattern, vals, X, thetas, dmesh=None, block=None, out=None, stream=None, grid=None):
+    """hdd_operator_apply_multi: Y[j] = (sum_q thetas[j, q] A_q) X[j] -- apply() at a parameter per row of X, the value
+    arrays read once per group of four rows.  X: device float64 [n_vec, cols] (rows may be strided), n_vec <=
+    MAX_VEC; thetas: host [n_vec, n_comp] (None: all ones).  Every other argument is apply()'s.  Row j is bit for bit
+    apply(..., X[j], theta=thetas[j]) on the same path; the tile kernel takes P1 with at most three and Q1 with one
+    value array, everything else the CSR kernel (then the bits of apply() with dmesh=None)."""
+    torch = _torch()
+    vals, n, ptrs, _, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, None, dmesh, block, grid)
+    if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1 or X.shape[1] != cols:
+        raise HddError("apply_multi: X must be float64 [n_vec, %d] with unit inner stride" % cols)
+    n_vec = X.shape[0]
+    th = _thetas("apply_multi", thetas, n_vec, n)
+    ldx = X.stride(0) if n_vec > 1 else max(cols, 1)
+    if out is None:
+        out = torch.empty((n_vec, rows), dtype=torch.float64, device=X.device)
+    if out.dim() != 2 or out.dtype != torch.float64 or out.stride(1) != 1 or out.shape != (n_vec, rows):
+        raise HddError("apply_multi: out must be float64 [n_vec, %d] with unit inner stride" % rows)
+    ldy = out.stride(0) if n_vec > 1 else max(rows, 1)
+    s = stream if stream is not None else torch.cuda.current_stream(X.device).cuda_stream
+    _check(lib().hdd_operator_apply_multi(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t),
+                                          ptrs, n, _p(th), n, None if rng is None else C.addressof(rng), X.data_ptr(), ldx,
+                                          out.data_ptr(), ldy, n_vec, C.c_void_p(s)), "hdd_operator_apply_multi")
+    return out
+
+
+def solve_multi(ctx, dpattern, vals, B, thetas, dmesh=None, block=None, X0=None, rtol=1e-8, atol=0.0, max_iter=10000,
+                precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None, grid=None):
+    """hdd_operator_solve_multi: (sum_q thetas[j, q] A_q) X[j] = B[j] for the n_rhs (1..MAX_VEC) rows of B in one call --
+    pyMOR's apply_inverse(V, mu=mu_j) over a parameter sample, the value arrays read once per group of four columns
+    and iteration.  thetas: host [n_rhs, n_comp] (None: all ones, then solve_batched bit for bit); every other argument
+    and the result (X, infos) are solve_batched()'s.  EVERY A(thetas[j]) MUST BE SYMMETRIC POSITIVE DEFINITE.  Column
+    j is bit for bit solve(..., B[j], theta=thetas[j], x0=X0[j]) on the same path (apply_multi's dispatch); a diagonal
+    block that is not positive definite at thetas[j] breaks column j alone down (SOLVE_BREAKDOWN, 0 iterations)."""
+    torch = _torch()
+    operator, keep, rows, n_rhs, ldb, X, opt, s = _solve_operands(True, dpattern, vals, None, dmesh, block, grid, B, X0, rtol, atol,
+                                                                  max_iter, precond, block_size, check_every, stream)
+    n_comp = operator[3]
+    th = _thetas("solve_multi", thetas, n_rhs, n_comp)
+    n_work = max(int(lib().hdd_operator_solve_multi_workspace(rows, opt.block_size, n_rhs)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=B.device)
+    ldh = max(int(max_iter), 0) + 1
+    hist = torch.zeros((n_rhs, ldh), dtype=torch.float64, device=B.device) if history else None
+    infos = (SolveInfo * n_rhs)()
+    _check(lib().hdd_operator_solve_multi(ctx.h, *operator[:4], _p(th), n_comp, operator[5], B.data_ptr(), ldb, X.data_ptr(),
+                                          max(rows, 1), n_rhs, C.addressof(opt), work.data_ptr(), n_work,
+                                          None if hist is None else hist.data_ptr(), ldh, C.addressof(infos), s),
+           "hdd_operator_solve_multi")
     out = []
     for j in range(n_rhs):
         i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)

@@ -578,6 +578,54 @@ int hdd_operator_solve_batched(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr
                                double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
                                void* stream);
 
+/* The same affine components at several parameters per call: column j has a theta of its own, theta_j = theta + j *
+ * ldt (host [n][ldt], ldt >= n_comp; NULL = all ones for every column).  This is the multi-query workload -- the
+ * snapshots and estimator residuals of a parametric study or a greedy loop are A(mu_j) = sum_q theta_q(mu_j) A_q on
+ * one pattern with one set of value arrays, which are read once per group of four columns instead of once per
+ * parameter.  Additive to ABI 8.
+ *
+ * hdd_operator_apply_multi: y_j = (sum_q theta_j[q] A_q) x_j, j < n_vec.  Every other argument, check, the range rule
+ * and "allocates nothing, no atomics" are hdd_operator_apply's.
+ * CONTRACT: column j is bit for bit what hdd_operator_apply gives for (theta_j, x_j) on the same path -- the matrix
+ * entry of column j is formed as there (theta_j[0] a_0, then one FMA per further component), then one FMA into the
+ * column's sum.  With theta NULL the call equals hdd_operator_apply's multi-vector result bit for bit.
+ * Dispatch: the tile kernel stages one LDS image per component, so it takes what hdd_operator_apply's tile path takes
+ * only for P1 with n_comp <= 3 and Q1 with n_comp == 1 (the images of a wave within the 64 KB of LDS a launch gets by
+ * default); everything else takes the CSR kernel (every n_comp <= HDD_MAX_COMP; the pattern then needs row_ptr / col)
+ * and is bit for bit hdd_operator_apply with mesh == NULL.  hdd_last_apply_kernel() names
+ * "apply_tile_multi_kernel<NB, NF, NV>" or "apply_csr_multi_kernel<G, NV>" (NV = 4 whatever n_vec is).
+ * HDD_ERR_INVALID also for a non-null theta with ldt < n_comp. */
+int hdd_operator_apply_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                             int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range,
+                             const double* d_x, int64_t ldx, double* d_y, int64_t ldy, int32_t n_vec, void* stream);
+/* doubles of workspace hdd_operator_solve_multi needs: hdd_operator_solve_batched_workspace with the inverse blocks
+ * n_rhs times (every column's preconditioner is that of its own theta_j).  0 for the same bad arguments. */
+int64_t hdd_operator_solve_multi_workspace(int64_t rows, int32_t block_size, int32_t n_rhs);
+/* hdd_operator_solve_batched with a theta per column: solves (sum_q theta_j[q] A_q) x_j = b_j for j < n_rhs in one
+ * call.  Every argument but theta / ldt, the range rule, the options, info, history, HDD_SOLVE_X0, the looks of the
+ * host, "allocates nothing" and "one stream at a time per context" are hdd_operator_solve_batched's; the dispatch is
+ * hdd_operator_apply_multi's.
+ * CONTRACT: column j ends with exactly the x, iterations, residual, rhs_norm, status and history that
+ * hdd_operator_solve gives for (theta_j, b_j, x0_j) with the same options on the same path -- the doubles bit for
+ * bit, whatever the other columns and their thetas are and whatever check_every is.  With theta NULL the call equals
+ * hdd_operator_solve_batched bit for bit.
+ * EVERY A(theta_j) MUST BE SYMMETRIC POSITIVE DEFINITE -- by calling the caller asserts this PER theta_j (a sum of
+ * components that is definite at one parameter need not be at another: DESIGN.md 4.7).
+ * Per-column breakdown: the inverse diagonal blocks are computed per column at theta_j into that column's slice of
+ * the workspace, with a count of blocks that are not positive definite per column.  Such a block at theta_j gives
+ * column j alone HDD_SOLVE_BREAKDOWN with 0 iterations, as the single solve at theta_j reports it; the other columns
+ * iterate on, frozen columns are not touched, and the call returns HDD_OK.  With HDD_SOLVE_X0 the initial residual is
+ * b_j - A(theta_j) x0_j by hdd_operator_apply_multi.  The columns run in groups of four.
+ * HDD_ERR_INVALID (every argument check precedes the first device call) for what hdd_operator_solve_batched rejects,
+ * a non-null theta with ldt < n_comp, n_work below hdd_operator_solve_multi_workspace.
+ * hdd_last_solve_kernels(): "apply_tile_multi_kernel<3, 3, 4, dot> + cg_update<3, 4, own> + cg_direction<4>" (without
+ * a preconditioner "cg_update<3, none, 4>"). */
+int hdd_operator_solve_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                             int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range,
+                             const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs,
+                             const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history,
+                             int64_t ldh, hdd_solve_info* info, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */
 /* GPU owns a contiguous range of subdomains and assembles their rows -- A_ss and A_ss,nn are written  */

@@ -792,6 +792,64 @@ class AffinelyDecomposedMatrix {
     for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
     return x;
   }
+  // x_j = A(mu_j)^-1 b_j for 1..HDD_MAX_VEC parameters at once (hdd_operator_solve_multi: pyMOR's apply_inverse(V,
+  // mu=mu_j) over a parameter sample): d_b [mus.size()][ldb], d_x [mus.size()][ldx] device arrays.  Column j is bit
+  // for bit what the single apply_inverse gives for (b_j, mu_j) on the same path; the value arrays are read once per
+  // group of four columns and iteration.  EVERY A(mu_j) must be symmetric positive definite (hdd.h).  Throws
+  // linear_solver_failed naming the first column that did not converge and its mu.
+  std::vector<hdd_solve_info> apply_inverse(const double* d_b, int64_t ldb, double* d_x, int64_t ldx, const std::vector<double>& mus,
+                                            const SolverOptions& options = SolverOptions(), const hdd_block_range* range = nullptr,
+                                            bool x0 = false, void* stream = nullptr) const
+  {
+    const int32_t n_rhs = int32_t(mus.size());
+    if (mus.empty() || mus.size() > size_t(HDD_MAX_VEC)) throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC parameters expected");
+    std::vector<const double*> v;
+    std::vector<double> thetas, theta;
+    for (const double mu : mus) {
+      v.clear();
+      theta.clear();
+      operands(mu, v, theta);
+      thetas.insert(thetas.end(), theta.begin(), theta.end());
+    }
+    const hdd_csr pat = pattern->csr();
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    const hdd_solve_options opt = solve_options(options, x0);
+    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_multi_workspace(rows, opt.block_size, n_rhs), 1);
+    internal::DeviceArray<double> work{size_t(n_work)};
+    std::vector<hdd_solve_info> infos(size_t(n_rhs), hdd_solve_info{});
+    internal::check(hdd_operator_solve_multi(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
+                                             thetas.data(), int64_t(v.size()), range, d_b, ldb, d_x, ldx, n_rhs, &opt, work.get(),
+                                             n_work, nullptr, 0, infos.data(), stream),
+                    "hdd_operator_solve_multi");
+    for (int32_t j = 0; j < n_rhs; ++j)
+      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
+        throw Stuff::Exceptions::linear_solver_failed(solver_failed(
+            infos[size_t(j)], " for column " + std::to_string(j) + " of " + std::to_string(n_rhs) + " (mu = " + std::to_string(mus[size_t(j)]) + ")"));
+    return infos;
+  }
+  std::vector<std::vector<double>> apply_inverse(const std::vector<std::vector<double>>& b, const std::vector<double>& mus,
+                                                 const SolverOptions& options = SolverOptions(),
+                                                 const hdd_block_range* range = nullptr,
+                                                 std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    if (b.empty() || b.size() > size_t(HDD_MAX_VEC) || b.size() != mus.size())
+      throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC right-hand sides and a mu for each expected");
+    for (const auto& bj : b)
+      if (int64_t(bj.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
+    const int64_t ld = std::max<int64_t>(rows + (rows & 1), 2);
+    internal::DeviceArray<double> db{size_t(ld) * b.size()}, dx{size_t(ld) * b.size()};
+    for (size_t j = 0; j < b.size(); ++j)
+      if (rows)
+        internal::hip_check(hipMemcpy(db.get() + j * size_t(ld), b[j].data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice),
+                            "apply_inverse");
+    const auto i = apply_inverse(db.get(), ld, dx.get(), ld, mus, options, range);
+    if (infos) *infos = i;
+    const auto all = dx.download();
+    std::vector<std::vector<double>> x(b.size());
+    for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
+    return x;
+  }
   // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
   // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
   void set_tile_mesh(const hdd_mesh& m, std::shared_ptr<internal::DeviceArray<int32_t>> nbrs)
@@ -1130,6 +1188,27 @@ class SWIPDG {
                                          std::vector<hdd_solve_info>* infos = nullptr) const
   {
     return system_matrix().apply_inverse(b, mu, options, nullptr, infos);
+  }
+  // ... at several parameters (1..HDD_MAX_VEC) in one device call (hdd_operator_solve_multi): the snapshots of a
+  // parametric study or a greedy loop.  b(mu_j) is combined per column as solve(mu) does; x(mu_j) is bit for bit
+  // solve(mu_j).  Throws linear_solver_failed naming the first column that did not converge and its mu.
+  std::vector<std::vector<double>> solve(const std::vector<double>& mus,
+                                         const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                         std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    const auto& b = rhs();
+    std::vector<std::vector<double>> bmus;
+    for (const double mu : mus) {
+      std::vector<double> bmu(size_t(b.size), 0.0);
+      if (b.affine) bmu = b.affine_part();
+      for (int q = 0; q < b.num_components(); ++q) {
+        const double th = b.coefficient(q).evaluate(mu);
+        const auto c = b.component(q);
+        for (size_t i = 0; i < bmu.size(); ++i) bmu[i] += th * c[i];
+      }
+      bmus.push_back(std::move(bmu));
+    }
+    return system_matrix().apply_inverse(bmus, mus, options, nullptr, infos);
   }
 
   // base.hh:272-291: only the products requested in the ctor (only_these_products, swipdg.hh:496-508)
@@ -1641,6 +1720,19 @@ class BlockSWIPDG : public SWIPDG {
     const int64_t nb = info_.nb;
     const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
     return system_matrix().apply_inverse(b, mu, options, &rng, infos);
+  }
+  // ... at a parameter per right-hand side: get_local_operator(ss)(mu_j)^-1 b_j in one device call
+  // (hdd_operator_solve_multi)
+  std::vector<std::vector<double>> solve_local(int ss, const std::vector<std::vector<double>>& b, const std::vector<double>& mus,
+                                               const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                               std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    range_check(ss);
+    int64_t a, e;
+    internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &e), "range");
+    const int64_t nb = info_.nb;
+    const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
+    return system_matrix().apply_inverse(b, mus, options, &rng, infos);
   }
 
   // block-swipdg.hh:678-685: the local vector of ss (local discretization rhs + boundary contributions) =

@@ -18,8 +18,12 @@ and when it breaks down the timing runs on the same mesh, pattern and coefficien
 --rhs N measures instead one hdd_operator_solve_batched call on N right-hand sides against N hdd_operator_solve calls
 on the same columns (the unchanged single-solve path), alternating over the rounds in the same process, per iteration
 as above; model per iteration 8 nnz n_comp + (BS + 1) / 2 8 n per group of four columns + 13 8 n per column.
+--thetas N measures, by the same protocol, one hdd_operator_solve_multi call of N columns at N different thetas
+against N hdd_operator_solve calls at those thetas: theta_j = (1, mu_j), mu_j spread over [0.3, 1], on the two
+components of c3 (definite from mu = 0.3 up once it is at 0.3), a scalar theta_j in [1, 2] on the one component of c2 /
+c4; model per iteration 8 nnz n_comp per group of four columns + (13 + (BS + 1) / 2) 8 n per column.
 Prints one JSON line per configuration; --out DIR also writes them to DIR/bench_solve.jsonl (--rhs:
-DIR/bench_solve_batched.jsonl)."""
+DIR/bench_solve_batched.jsonl, --thetas: DIR/bench_solve_multi.jsonl)."""
 import argparse
 import json
 import math
@@ -86,15 +90,25 @@ def build(name, n):
 
 def run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, scale, gen):
     """--rhs N: one hdd_operator_solve_batched call on N right-hand sides against N hdd_operator_solve calls (the
-    unchanged single-solve path) on the same columns, alternating over the rounds in this process"""
-    n, nnz, nc, N, iters = dp.t.n_rows, dp.nnz, len(vals), args.rhs, args.iters
+    unchanged single-solve path) on the same columns, alternating over the rounds in this process.  --thetas N: one
+    hdd_operator_solve_multi call against N single solves at the columns' own thetas, likewise."""
+    multi = args.thetas > 0
+    n, nnz, nc, N, iters = dp.t.n_rows, dp.nnz, len(vals), args.thetas or args.rhs, args.iters
     B = torch.randn((N, n), dtype=torch.float64, device="cuda", generator=gen)
+    if multi and nc == 2:
+        thetas = np.stack([np.ones(N), np.linspace(0.3, 1.0, N)], axis=1)
+    elif multi:
+        thetas = np.linspace(1.0, 2.0, N).reshape(N, 1)
+    else:
+        thetas = np.tile(np.asarray(theta, np.float64), (N, 1))
 
     def batched(k):
+        if multi:
+            return H.solve_multi(ctx, dp, vals, B, thetas, dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
         return H.solve_batched(ctx, dp, vals, B, theta=theta, dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
 
     def singles(k):
-        return [H.solve(ctx, dp, vals, B[j], theta=theta, dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
+        return [H.solve(ctx, dp, vals, B[j], theta=thetas[j], dmesh=dm, rtol=0.0, max_iter=k, check_every=max(k, 1))
                 for j in range(N)]
 
     def timed(fn, k):
@@ -123,9 +137,13 @@ def run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, 
     identical = all(bool(torch.equal(X[j].view(torch.int64), one[j][0].view(torch.int64))) for j in range(N))
     med = {k: float(np.median(v)) for k, v in per.items()}
     groups = (N + 3) // 4
-    model_b = groups * (8 * nnz * nc + (nb + 1) / 2 * 8 * n) + N * 13 * 8 * n
+    if multi:   # every column has inverse blocks of its own
+        model_b = groups * 8 * nnz * nc + N * (13 + (nb + 1) / 2) * 8 * n
+    else:
+        model_b = groups * (8 * nnz * nc + (nb + 1) / 2 * 8 * n) + N * 13 * 8 * n
     model_s = N * (8 * nnz * nc + (13 + (nb + 1) / 2) * 8 * n)
     res = dict(config=label, n_rows=n, nnz=nnz, n_comp=nc, block_size=nb, n_rhs=N, iters=iters, rounds=args.rounds,
+               mode="thetas" if multi else "rhs", thetas=thetas.tolist(),
                reference_penalties=reference, sigma_scale=scale, kernels=names,
                status=[i.status for i in infos], iterations=[i.iterations for i in infos],
                columns_bit_identical_to_singles=identical,
@@ -154,7 +172,7 @@ def run_config(args):
         scale *= args.sigma_scale
         vals = assemble(scale, vals)
         _, i0 = H.solve(ctx, dp, vals, b, theta=theta, dmesh=dm, rtol=0.0, max_iter=iters, check_every=iters)
-    if args.rhs:
+    if args.rhs or args.thetas:
         return run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, scale, gen)
     Dinv = inverse_blocks(torch, loc, dm, dp, vals, theta)
 
@@ -228,6 +246,8 @@ def main():
     ap.add_argument("--converge", type=int, default=0, help="also solve to rtol 1e-8 with at most this many iterations")
     ap.add_argument("--rhs", type=int, default=0, help="N > 0: time one batched solve of N right-hand sides against N single "
                     "solves instead (bench_solve_batched.jsonl)")
+    ap.add_argument("--thetas", type=int, default=0, help="N > 0: time one solve_multi of N columns at N thetas against N single "
+                    "solves at those thetas instead (bench_solve_multi.jsonl)")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per configuration (child process)")
     ap.add_argument("--out", default=None, help="directory for bench_solve.jsonl")
     args = ap.parse_args()
@@ -237,7 +257,8 @@ def main():
     lines = []
     for c in args.configs:
         cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--n", str(args.n), "--iters", str(args.iters),
-               "--rounds", str(args.rounds), "--converge", str(args.converge), "--sigma-scale", str(args.sigma_scale), "--rhs", str(args.rhs)]
+               "--rounds", str(args.rounds), "--converge", str(args.converge), "--sigma-scale", str(args.sigma_scale), "--rhs", str(args.rhs),
+               "--thetas", str(args.thetas)]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
@@ -252,7 +273,7 @@ def main():
                 print(ln, flush=True)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, "bench_solve_batched.jsonl" if args.rhs else "bench_solve.jsonl"), "w") as f:
+        with open(os.path.join(args.out, "bench_solve_multi.jsonl" if args.thetas else "bench_solve_batched.jsonl" if args.rhs else "bench_solve.jsonl"), "w") as f:
             f.write("\n".join(lines) + "\n")
     return 0
 
