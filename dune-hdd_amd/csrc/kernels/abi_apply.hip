@@ -1,11 +1,12 @@
 // dune-hdd_amd/csrc/kernels/abi_apply.hip -- C ABI: operator application on the assembled value arrays
-// (hdd_operator_apply, hdd_operator_apply2; kernels in apply_kernels.hh): what pyMOR's apply / apply2 and LRBMS's
+// (hdd_operator_apply, hdd_operator_apply_multi, hdd_operator_apply2; kernels in apply_kernels.hh): what pyMOR's apply / apply2 and LRBMS's
 // local / coupling operators need from the containers SWIPDG::init() fills (base.hh:45, 260-264, 327-367;
 // block-swipdg.hh:625-676), on the device, with the theta-lincomb fused and block ranges applied in place.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <string>
 
 #include "apply_plan.hh"
 
@@ -14,18 +15,19 @@ using hdd::abi::ApplyPlan;
 using hdd::abi::fail;
 using hdd::abi::plan_apply;
 using hdd::abi::run_apply;
+using hdd::abi::ApplyThetas;
 namespace dev = hdd::dev;
 
 namespace {
-const char*& last_apply_kernel_slot()
+std::string& last_apply_kernel_slot()
 {
-  thread_local const char* name = "";
+  thread_local std::string name;
   return name;
 }
 }  // namespace
 
 int hdd::abi::plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
-               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P)
+               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P, bool per_vector)
 {
   if (!ctx || !pattern || !d_vals) return fail(HDD_ERR_INVALID, who, "null argument");
   if (n_comp < 1 || n_comp > HDD_MAX_COMP) return fail(HDD_ERR_INVALID, who, "n_comp outside 1..HDD_MAX_COMP");
@@ -80,116 +82,42 @@ int hdd::abi::plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, co
       a.ce_end = rg.col_end / nb;
     }
   }
-  if (!P.tile) {
-    if (!pattern->row_ptr || !pattern->col) return fail(HDD_ERR_INVALID, who, "pattern without row_ptr / col");
-    P.short_rows = pattern->n_rows == 0 || pattern->nnz / std::max<int64_t>(pattern->n_rows, 1) <= 32;
-  }
-  return HDD_OK;
-}
-
-namespace {
-template <int NB, int NF>
-hipError_t launch_tile(const hdd_ctx* ctx, const dev::ApplyArgs& a, bool multi, hipStream_t s)
-{
-  using I = dev::ApplyImage<NB, NF>;
-  const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
-  const int64_t G = hdd::abi::apply_tile_grid<NB, NF>(ctx, n_tiles);
-  static const char* names[2] = {NB == 3 ? "apply_tile_kernel<3, 3, 1>" : "apply_tile_kernel<4, 4, 1>",
-                                 NB == 3 ? "apply_tile_kernel<3, 3, 4>" : "apply_tile_kernel<4, 4, 4>"};
-  last_apply_kernel_slot() = names[multi];
-  if (multi)
-    hipLaunchKernelGGL((dev::apply_tile_kernel<NB, NF, dev::APPLY_NV>), dim3(unsigned(G)), dim3(64), I::BYTES, s, a, n_tiles);
-  else
-    hipLaunchKernelGGL((dev::apply_tile_kernel<NB, NF, 1>), dim3(unsigned(G)), dim3(64), I::BYTES, s, a, n_tiles);
-  return hipGetLastError();
-}
-
-template <int G>
-hipError_t launch_csr(const dev::ApplyArgs& a, bool multi, hipStream_t s)
-{
-  const unsigned grid = unsigned(hdd::abi::apply_csr_grid<G>(a.row_end - a.row_begin));
-  static const char* names[2] = {G == 8 ? "apply_csr_kernel<8, 1>" : "apply_csr_kernel<64, 1>",
-                                 G == 8 ? "apply_csr_kernel<8, 4>" : "apply_csr_kernel<64, 4>"};
-  last_apply_kernel_slot() = names[multi];
-  if (multi) hipLaunchKernelGGL((dev::apply_csr_kernel<G, dev::APPLY_NV>), dim3(grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL((dev::apply_csr_kernel<G, 1>), dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-}  // namespace
-
-int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
-              int32_t n_vec, void* stream)
-{
-  if (P.a.row_end == P.a.row_begin) return HDD_OK;
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return hip_fail(e, who);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int v0 = 0; v0 < n_vec; v0 += dev::APPLY_NV) {
-    dev::ApplyArgs a = P.a;
-    a.nv = std::min<int>(dev::APPLY_NV, n_vec - v0);
-    a.x = d_x + int64_t(v0) * ldx;
-    a.ldx = ldx;
-    a.y = d_y + int64_t(v0) * ldy;
-    a.ldy = ldy;
-    const bool multi = a.nv > 1;
-    if (P.tile) e = P.nb == 3 ? launch_tile<3, 3>(ctx, a, multi, s) : launch_tile<4, 4>(ctx, a, multi, s);
-    else e = P.short_rows ? launch_csr<8>(a, multi, s) : launch_csr<64>(a, multi, s);
-    if (e != hipSuccess) return hip_fail(e, who);
-  }
-  return HDD_OK;
-}
-
-int hdd::abi::plan_apply_multi(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
-                               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P)
-{
-  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, P)) return rc;
-  if (P.tile && !apply_multi_tile_fits(P.nb, n_comp)) {
-    if (!pattern->row_ptr || !pattern->col) return fail(HDD_ERR_INVALID, who, "pattern without row_ptr / col (component images beyond the LDS)");
+  // the generic path -- also with a theta per vector where the component images do not fit the LDS
+  const bool no_images = per_vector && P.tile && !(P.nb == 3 ? n_comp <= 3 : n_comp == 1);
+  if (!P.tile || no_images) {
+    if (!pattern->row_ptr || !pattern->col)
+      return fail(HDD_ERR_INVALID, who, no_images ? "pattern without row_ptr / col (component images beyond the LDS)" : "pattern without row_ptr / col");
     P.tile = false;
     P.short_rows = pattern->n_rows == 0 || pattern->nnz / std::max<int64_t>(pattern->n_rows, 1) <= 32;
   }
   return HDD_OK;
 }
 
-void hdd::abi::apply_multi_thetas(dev::ApplyMultiArgs& ma, const double* theta, int64_t ldt, int v0)
+void hdd::abi::apply_multi_thetas(dev::ApplyMultiArgs& ma, const ApplyThetas& T, int v0)
 {
   for (int v = 0; v < dev::APPLY_NV; ++v) {
     const int64_t j = v0 + (v < ma.a.nv ? v : 0);
-    for (int q = 0; q < HDD_MAX_COMP; ++q) ma.theta[v][q] = q < ma.a.n_comp ? (theta ? theta[j * ldt + q] : 1.0) : 0.0;
+    for (int q = 0; q < HDD_MAX_COMP; ++q) ma.theta[v][q] = q < ma.a.n_comp ? (T.theta ? T.theta[j * T.ldt + q] : 1.0) : 0.0;
   }
 }
 
-namespace {
-template <int NB, int NF, int NC>
-hipError_t launch_tile_multi(const hdd_ctx* ctx, const dev::ApplyMultiArgs& ma, hipStream_t s)
+void hdd::abi::apply_kernel_name(std::string& out, const ApplyPlan& P, bool per_vector, int nv, bool dot)
 {
-  using I = dev::ApplyImage<NB, NF>;
-  static_assert(NC * I::BYTES <= 64 * 1024, "the dynamic LDS a launch gets without raising the kernel's attribute");
-  const int64_t n_tiles = (ma.a.e_end - ma.a.e_begin + 63) / 64;
-  const int64_t G = hdd::abi::apply_tile_grid<NB, NF>(ctx, n_tiles);
-  last_apply_kernel_slot() = NB == 3 ? "apply_tile_multi_kernel<3, 3, 4>" : "apply_tile_multi_kernel<4, 4, 4>";
-  hipLaunchKernelGGL((dev::apply_tile_multi_kernel<NB, NF, dev::APPLY_NV, false, NC>), dim3(unsigned(G)), dim3(64), NC * I::BYTES, s, ma, n_tiles);
-  return hipGetLastError();
+  out += P.tile ? "apply_tile_" : "apply_csr_";
+  out += per_vector ? "multi_kernel<" : "kernel<";
+  out += P.tile ? (P.nb == 3 ? "3, 3, " : "4, 4, ") : (P.short_rows ? "8, " : "64, ");
+  out += char('0' + nv);
+  out += dot ? ", dot>" : ">";
 }
 
-template <int G>
-hipError_t launch_csr_multi(const dev::ApplyMultiArgs& ma, hipStream_t s)
+int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const ApplyThetas* T, const double* d_x, int64_t ldx,
+                        double* d_y, int64_t ldy, int32_t n_vec, void* stream)
 {
-  const unsigned grid = unsigned(hdd::abi::apply_csr_grid<G>(ma.a.row_end - ma.a.row_begin));
-  last_apply_kernel_slot() = G == 8 ? "apply_csr_multi_kernel<8, 4>" : "apply_csr_multi_kernel<64, 4>";
-  hipLaunchKernelGGL((dev::apply_csr_multi_kernel<G, dev::APPLY_NV>), dim3(grid), dim3(256), 0, s, ma);
-  return hipGetLastError();
-}
-}  // namespace
-
-int hdd::abi::run_apply_multi(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* theta, int64_t ldt, const double* d_x, int64_t ldx,
-                              double* d_y, int64_t ldy, int32_t n_vec, void* stream)
-{
-  if (P.a.row_end == P.a.row_begin) return HDD_OK;
+  if (P.rows() == 0) return HDD_OK;
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_fail(e, who);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t grid = apply_grid(ctx, P);
   for (int v0 = 0; v0 < n_vec; v0 += dev::APPLY_NV) {
     dev::ApplyMultiArgs ma;
     dev::ApplyArgs& a = ma.a;
@@ -199,31 +127,45 @@ int hdd::abi::run_apply_multi(const char* who, hdd_ctx* ctx, ApplyPlan& P, const
     a.ldx = ldx;
     a.y = d_y + int64_t(v0) * ldy;
     a.ldy = ldy;
-    apply_multi_thetas(ma, theta, ldt, v0);
-    if (P.tile && P.nb == 3)
-      e = a.n_comp == 1 ? launch_tile_multi<3, 3, 1>(ctx, ma, s) : a.n_comp == 2 ? launch_tile_multi<3, 3, 2>(ctx, ma, s) : launch_tile_multi<3, 3, 3>(ctx, ma, s);
-    else if (P.tile) e = launch_tile_multi<4, 4, 1>(ctx, ma, s);
-    else e = P.short_rows ? launch_csr_multi<8>(ma, s) : launch_csr_multi<64>(ma, s);
+    const int nv = T || a.nv > 1 ? dev::APPLY_NV : 1;   // the instantiation's
+    last_apply_kernel_slot().clear();
+    apply_kernel_name(last_apply_kernel_slot(), P, T != nullptr, nv, false);
+    if (T) {
+      apply_multi_thetas(ma, *T, v0);
+      e = launch_apply<dev::APPLY_NV, false>(P, ma, grid, s);
+    } else {
+      e = nv > 1 ? launch_apply<dev::APPLY_NV, false>(P, a, grid, s) : launch_apply<1, false>(P, a, grid, s);
+    }
     if (e != hipSuccess) return hip_fail(e, who);
   }
   return HDD_OK;
 }
 
-extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot(); }
+extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot().c_str(); }
+
+namespace {
+// hdd_operator_apply (per_vector false: theta is [n_comp]) and hdd_operator_apply_multi (theta is [n_vec][ldt])
+int apply(const char* who, bool per_vector, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+          int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range, const double* d_x, int64_t ldx,
+          double* d_y, int64_t ldy, int32_t n_vec, void* stream)
+{
+  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_vec < 1 || n_vec > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_vec outside 1..HDD_MAX_VEC");
+  ApplyPlan P;
+  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, per_vector ? nullptr : theta, range, P, per_vector)) return rc;
+  if (per_vector && theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
+  if (ldx < P.a.col_end - P.a.col_begin || ldy < P.rows())
+    return fail(HDD_ERR_INVALID, who, "ldx / ldy smaller than the range");
+  const ApplyThetas T{theta, ldt};
+  return run_apply(who, ctx, P, per_vector ? &T : nullptr, d_x, ldx, d_y, ldy, n_vec, stream);
+}
+}  // namespace
 
 extern "C" int hdd_operator_apply_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
                                         int32_t n_comp, const double* theta, int64_t ldt, const hdd_block_range* range,
                                         const double* d_x, int64_t ldx, double* d_y, int64_t ldy, int32_t n_vec, void* stream)
 {
-  const char* who = "hdd_operator_apply_multi";
-  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
-  if (n_vec < 1 || n_vec > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_vec outside 1..HDD_MAX_VEC");
-  ApplyPlan P;
-  if (int rc = hdd::abi::plan_apply_multi(who, ctx, mesh, pattern, d_vals, n_comp, nullptr, range, P)) return rc;
-  if (theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
-  if (ldx < P.a.col_end - P.a.col_begin || ldy < P.a.row_end - P.a.row_begin)
-    return fail(HDD_ERR_INVALID, who, "ldx / ldy smaller than the range");
-  return hdd::abi::run_apply_multi(who, ctx, P, theta, ldt, d_x, ldx, d_y, ldy, n_vec, stream);
+  return apply("hdd_operator_apply_multi", true, ctx, mesh, pattern, d_vals, n_comp, theta, ldt, range, d_x, ldx, d_y, ldy, n_vec, stream);
 }
 
 extern "C" int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,
@@ -231,14 +173,7 @@ extern "C" int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
                                   const hdd_block_range* range, const double* d_x, int64_t ldx, double* d_y,
                                   int64_t ldy, int32_t n_vec, void* stream)
 {
-  const char* who = "hdd_operator_apply";
-  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
-  if (n_vec < 1 || n_vec > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_vec outside 1..HDD_MAX_VEC");
-  ApplyPlan P;
-  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, P)) return rc;
-  if (ldx < P.a.col_end - P.a.col_begin || ldy < P.a.row_end - P.a.row_begin)
-    return fail(HDD_ERR_INVALID, who, "ldx / ldy smaller than the range");
-  return run_apply(who, ctx, P, d_x, ldx, d_y, ldy, n_vec, stream);
+  return apply("hdd_operator_apply", false, ctx, mesh, pattern, d_vals, n_comp, theta, 0, range, d_x, ldx, d_y, ldy, n_vec, stream);
 }
 
 extern "C" int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,
@@ -257,7 +192,7 @@ extern "C" int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd
   if (ldu < P.a.col_end - P.a.col_begin || ldv < rows || ldw < rows)
     return fail(HDD_ERR_INVALID, who, "ldv / ldu / ldw smaller than the range");
   if (!ctx->apply2_ws) return fail(HDD_ERR_INVALID, who, "context without its reduction buffer");
-  if (int rc = run_apply(who, ctx, P, d_u, ldu, d_work, ldw, n_u, stream)) return rc;
+  if (int rc = run_apply(who, ctx, P, nullptr, d_u, ldu, d_work, ldw, n_u, stream)) return rc;
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_fail(e, who);
   hipStream_t s = static_cast<hipStream_t>(stream);

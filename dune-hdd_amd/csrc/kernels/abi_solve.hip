@@ -93,8 +93,8 @@ struct Solve {
   double *part_pq, *part_rz, *part_rr, *part_bb, *p, *q, *r, *z, *dinv, *x, *history;
   // a theta per column (hdd_operator_solve_multi): the caller's [n_rhs][ldt] (NULL: ones), column c's inverse blocks
   // at dinv + c * ld_dinv, its partial counts of indefinite blocks at part_pq + c * bad_stride; else zeros
-  const double* thetas;
-  int64_t ldt, ld_dinv, bad_stride;
+  hdd::abi::ApplyThetas thetas;
+  int64_t ld_dinv, bad_stride;
 
   void carve(double* w, int64_t head)
   {
@@ -122,21 +122,6 @@ struct Solve {
   }
 };
 
-// workgroups of the DOT apply (= partial sums it writes)
-int64_t dot_grid(const hdd_ctx* ctx, const ApplyPlan& P)
-{
-  const int64_t rows = P.a.row_end - P.a.row_begin;
-  int64_t G;
-  if (P.tile) {
-    const int64_t n_tiles = (P.a.e_end - P.a.e_begin + 63) / 64;
-    G = P.nb == 3 ? hdd::abi::apply_tile_grid<3, 3>(ctx, n_tiles) : hdd::abi::apply_tile_grid<4, 4>(ctx, n_tiles);
-    if (G > dev::SOLVE_PARTS) G = dev::SOLVE_PARTS & ~7;   // tile_range: a multiple of 8 below the tile count
-  } else {
-    G = std::min<int64_t>(P.short_rows ? hdd::abi::apply_csr_grid<8>(rows) : hdd::abi::apply_csr_grid<64>(rows), 2048);
-  }
-  return G;
-}
-
 // Every argument check of the entries, in the order of their messages, without a device call; fills S except its
 // workspace pointers.  The single solve has n_rhs = 1 and dense leading dimensions, so the batch's checks pass.
 // theta is [n_comp], with E.own [n_rhs][ldt].
@@ -148,9 +133,7 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   const char* who = E.who;
   if (!d_b || !d_x || !opt || !d_work || !info) return fail(HDD_ERR_INVALID, who, "null argument");
   if (n_rhs < 1 || n_rhs > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_rhs outside 1..HDD_MAX_VEC");
-  if (int rc = E.own ? hdd::abi::plan_apply_multi(who, ctx, mesh, pattern, d_vals, n_comp, nullptr, range, S.P)
-                     : hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, range, S.P))
-    return rc;
+  if (int rc = hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, E.own ? nullptr : theta, range, S.P, E.own)) return rc;
   if (E.own && theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
   const dev::ApplyArgs& a = S.P.a;
   if (a.row_begin != a.col_begin || a.row_end != a.col_end)
@@ -191,12 +174,11 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   S.rows = rows, S.ldb = ldb, S.ldx = ldx, S.ldw = even(rows), S.ldh = ldh;
   S.n_parts = std::max<int64_t>(1, std::min<int64_t>((rows / bs + 255) / 256, 2048));
   S.dgrid = std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, 4096));
-  S.n_pq = int32_t(dot_grid(ctx, S.P));
+  S.n_pq = int32_t(hdd::abi::dot_grid(ctx, S.P, dev::SOLVE_PARTS));
   S.s = static_cast<hipStream_t>(stream);
   S.x = d_x;
   S.history = d_history;
-  S.thetas = E.own ? theta : nullptr;
-  S.ldt = ldt;
+  S.thetas = hdd::abi::ApplyThetas{E.own ? theta : nullptr, ldt};
   S.ld_dinv = E.own ? blocks_doubles(rows, bs) : 0;
   S.bad_stride = E.own ? dev::SOLVE_PARTS : 0;
   // the 16-byte paths need every column of x aligned
@@ -230,41 +212,12 @@ hipError_t with_block(const Solve& S, F&& f)
   }
 }
 
-// q = A p with p . q into part_pq for nv <= NV columns (leading dimension ldw), iteration k; the launch returns at
-// once when *done_at <= k.  The grid is n_pq for every NV: the bits of p . q rest on it.
+// q = A p with p . q into part_pq for nv <= NV columns (leading dimension ldw; with E.own the group's columns begin at
+// g0 and have their thetas), iteration k; the launch returns at once when *done_at <= k.  The grid is n_pq for every
+// NV: the bits of p . q rest on it.
 template <int NV>
-hipError_t launch_apply_dot(const Solve& S, const double* p, double* q, int nv, double* part_pq, const int32_t* done_at, int k)
-{
-  dev::ApplyArgs a = S.P.a;
-  a.nv = nv;
-  a.x = p;
-  a.y = q;
-  a.ldx = a.ldy = S.ldw;
-  a.partial = part_pq;
-  a.done_at = done_at;
-  a.iteration = k;
-  const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
-  if (S.P.tile && S.P.nb == 3)
-    hipLaunchKernelGGL((dev::apply_tile_kernel<3, 3, NV, true>), grid(S.n_pq), dim3(64), (dev::ApplyImage<3, 3>::BYTES), S.s, a, n_tiles);
-  else if (S.P.tile)
-    hipLaunchKernelGGL((dev::apply_tile_kernel<4, 4, NV, true>), grid(S.n_pq), dim3(64), (dev::ApplyImage<4, 4>::BYTES), S.s, a, n_tiles);
-  else if (S.P.short_rows)
-    hipLaunchKernelGGL((dev::apply_csr_kernel<8, NV, true>), grid(S.n_pq), dim3(256), 0, S.s, a);
-  else
-    hipLaunchKernelGGL((dev::apply_csr_kernel<64, NV, true>), grid(S.n_pq), dim3(256), 0, S.s, a);
-  return hipGetLastError();
-}
-
-// launch_apply_dot<APPLY_NV> with a theta per column: the group's columns begin at g0
-template <int NC>
-void launch_tile_dot_multi(const Solve& S, const dev::ApplyMultiArgs& ma, int64_t n_tiles)
-{
-  using I = dev::ApplyImage<3, 3>;
-  static_assert(NC * I::BYTES <= 64 * 1024, "the dynamic LDS a launch gets without raising the kernel's attribute");
-  hipLaunchKernelGGL((dev::apply_tile_multi_kernel<3, 3, NVB, true, NC>), grid(S.n_pq), dim3(64), NC * I::BYTES, S.s, ma, n_tiles);
-}
-
-hipError_t launch_apply_dot_multi(const Solve& S, int g0, const double* p, double* q, int nv, double* part_pq, const int32_t* done_at, int k)
+hipError_t launch_apply_dot(const Entry& E, const Solve& S, int g0, const double* p, double* q, int nv, double* part_pq,
+                            const int32_t* done_at, int k)
 {
   dev::ApplyMultiArgs ma;
   dev::ApplyArgs& a = ma.a;
@@ -276,30 +229,23 @@ hipError_t launch_apply_dot_multi(const Solve& S, int g0, const double* p, doubl
   a.partial = part_pq;
   a.done_at = done_at;
   a.iteration = k;
-  hdd::abi::apply_multi_thetas(ma, S.thetas, S.ldt, g0);
-  const int64_t n_tiles = (a.e_end - a.e_begin + 63) / 64;
-  if (S.P.tile && S.P.nb == 3) {
-    if (a.n_comp == 1) launch_tile_dot_multi<1>(S, ma, n_tiles);
-    else if (a.n_comp == 2) launch_tile_dot_multi<2>(S, ma, n_tiles);
-    else launch_tile_dot_multi<3>(S, ma, n_tiles);
-  } else if (S.P.tile)
-    hipLaunchKernelGGL((dev::apply_tile_multi_kernel<4, 4, NVB, true, 1>), grid(S.n_pq), dim3(64), (dev::ApplyImage<4, 4>::BYTES), S.s, ma, n_tiles);
-  else if (S.P.short_rows)
-    hipLaunchKernelGGL((dev::apply_csr_multi_kernel<8, NVB, true>), grid(S.n_pq), dim3(256), 0, S.s, ma);
-  else
-    hipLaunchKernelGGL((dev::apply_csr_multi_kernel<64, NVB, true>), grid(S.n_pq), dim3(256), 0, S.s, ma);
-  return hipGetLastError();
+  if constexpr (NV == NVB)   // only the batch has a theta per column: no one-vector instantiation of the multi kernels
+    if (E.own) {
+      hdd::abi::apply_multi_thetas(ma, S.thetas, g0);
+      return hdd::abi::launch_apply<NV, true>(S.P, ma, S.n_pq, S.s);
+    }
+  return hdd::abi::launch_apply<NV, true>(S.P, a, S.n_pq, S.s);
 }
 
 // names of the iteration's kernels; the batch's vector count is the instantiation's (APPLY_NV), not n_rhs
 void name_kernels(const Entry& E, const Solve& S)
 {
   const bool batched = !E.dense;
-  const std::string nv = std::to_string(batched ? NVB : 1), multi = E.own ? "multi_" : "";
+  const std::string nv = std::to_string(batched ? NVB : 1);
   std::string& nm = last_solve_kernels_slot();
-  if (S.P.tile) nm = "apply_tile_" + multi + (S.P.nb == 3 ? "kernel<3, 3, " : "kernel<4, 4, ");
-  else nm = "apply_csr_" + multi + (S.P.short_rows ? "kernel<8, " : "kernel<64, ");
-  nm += nv + ", dot> + cg_update<" + std::to_string(S.bs) + (S.pre ? "" : ", none");
+  nm.clear();
+  hdd::abi::apply_kernel_name(nm, S.P, E.own, batched ? NVB : 1, true);
+  nm += " + cg_update<" + std::to_string(S.bs) + (S.pre ? "" : ", none");
   nm += batched ? ", " + nv + (E.own && S.pre ? ", own" : "") + "> + cg_direction<" + nv + ">" : "> + cg_direction";
 }
 
@@ -314,7 +260,7 @@ int setup(const Entry& E, hdd_ctx* ctx, Solve& S, const double* d_b)
   name_kernels(E, S);
   for (int c = 0; S.pre && c < (E.own ? S.n_rhs : 1); ++c) {
     dev::ApplyArgs a = S.P.a;
-    for (int q = 0; E.own && q < a.n_comp; ++q) a.theta[q] = S.thetas ? S.thetas[c * S.ldt + q] : 1.0;
+    for (int q = 0; E.own && q < a.n_comp; ++q) a.theta[q] = S.thetas.theta ? S.thetas.theta[c * S.thetas.ldt + q] : 1.0;
     double *dinv = S.dinv + c * S.ld_dinv, *part_bad = S.part_pq + c * S.bad_stride;
     e = with_block(S, [&](auto BS, auto, auto) {
       if (!S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_csr_kernel<BS()>), grid(S.n_parts), dim3(256), 0, S.s, a, dinv, part_bad);
@@ -325,9 +271,7 @@ int setup(const Entry& E, hdd_ctx* ctx, Solve& S, const double* d_b)
     if (e != hipSuccess) return hip_fail(e, E.who);
   }
   if (S.x0)
-    if (int rc = E.own ? hdd::abi::run_apply_multi(E.who, ctx, S.P, S.thetas, S.ldt, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s)
-                       : hdd::abi::run_apply(E.who, ctx, S.P, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s))
-      return rc;
+    if (int rc = hdd::abi::run_apply(E.who, ctx, S.P, E.own ? &S.thetas : nullptr, S.x, S.ldx, S.q, S.ldw, S.n_rhs, S.s)) return rc;
   for (int c = 0; c < S.n_rhs; ++c) {
     e = with_block(S, [&](auto BS, auto PRE, auto A16) {
       hipLaunchKernelGGL((dev::cg_init_kernel<BS(), PRE(), A16()>), grid(S.n_parts), dim3(256), 0, S.s, S.column(c), d_b + c * S.ldb, S.x0);
@@ -416,7 +360,7 @@ extern "C" int hdd_operator_solve(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
   if (e != hipSuccess) return hip_fail(e, E.who);
   int k;
   const int rc = iterate(E, ctx, S, opt, sizeof(dev::SolveState), k, [&](int k) {
-    hipError_t e = launch_apply_dot<1>(S, v.p, v.q, 1, v.part_pq, &v.state->done_at, k);
+    hipError_t e = launch_apply_dot<1>(E, S, 0, v.p, v.q, 1, v.part_pq, &v.state->done_at, k);
     if (e != hipSuccess) return e;
     return with_block(S, [&](auto BS, auto PRE, auto A16) {
       hipLaunchKernelGGL((dev::cg_update_kernel<BS(), PRE(), A16()>), grid(S.n_parts), dim3(256), 0, S.s, v, k);
@@ -454,7 +398,7 @@ int solve_columns(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
     hipError_t e = hipSuccess;
     for (int g0 = 0; g0 < n_rhs && e == hipSuccess; g0 += NVB) {
       const dev::SolveBatch v = S.group(g0);
-      e = E.own ? launch_apply_dot_multi(S, g0, v.p, v.q, v.nv, v.part_pq, v.stop, k) : launch_apply_dot<NVB>(S, v.p, v.q, v.nv, v.part_pq, v.stop, k);
+      e = launch_apply_dot<NVB>(E, S, g0, v.p, v.q, v.nv, v.part_pq, v.stop, k);
       if (e != hipSuccess) return e;
       e = with_block(S, [&](auto BS, auto PRE, auto A16) {
         if (E.own && PRE()) hipLaunchKernelGGL((dev::cg_update_batched_kernel<BS(), PRE(), A16(), NVB, PRE()>), grid(S.n_parts), dim3(256), 0, S.s, v, k);

@@ -1,12 +1,11 @@
 // dune-hdd_amd/csrc/kernels/apply_kernels.hh -- operator application y = (sum_q theta_q A_q) x on the assembled
-// value arrays (hdd_operator_apply / hdd_operator_apply2, abi_apply.hip).
+// value arrays (hdd_operator_apply / _apply_multi / _apply2, abi_apply.hip; launched by launch_apply, apply_plan.hh).
 //
-// apply_tile_kernel -- the assembler run backwards, for 2d P1 / Q1 SWIPDG patterns in local == global numbering.  One
+// apply_tile_body -- the assembler run backwards, for 2d P1 / Q1 SWIPDG patterns in local == global numbering.  One
 //   wave owns a tile of 64 consecutive elements of the row range (persistent over tiles, the assembler's tile_range
 //   XCD sweep).  The tile's row blocks are ONE contiguous CSR value range [elem_ptr[t0], elem_ptr[t0 + 64)): the wave
-//   streams it with aligned 16-byte buffer loads (origin base_al = base & ~1, as the assembler's image), combines the
-//   components with theta on the way (one image whatever n_comp) and writes it into an LDS image (XOR-swizzled
-//   against the bank conflicts of row blocks 36 / 80 values apart, apply_swz).  Lane l then takes
+//   streams it with aligned 16-byte buffer loads (origin base_al = base & ~1, as the assembler's image) into an LDS
+//   image (XOR-swizzled against the bank conflicts of row blocks 36 / 80 values apart, apply_swz).  Lane l then takes
 //   element t0 + l: its row block starts at the ballot prefix sum of the block counts (tile_offset), its block
 //   columns are its own id and its face neighbours' ids sorted ascending -- the ordering hdd_dg_pattern_fill gave the
 //   blocks -- so neither col nor row_ptr is read: 8 B per nonzero instead of 12.  Blocks whose element lies outside
@@ -14,8 +13,23 @@
 //   go through buffer resources with the true sizes: an index the mesh got wrong reads zero instead of faulting.
 //   No pipelining across tiles inside a wave: several waves per CU (8 P1 images, 4 Q1 images fit the LDS) overlap
 //   one wave's loads with another's arithmetic, and a wave has up to 20 KB of loads in flight by itself.
-// apply_csr_kernel -- plain CSR on row_ptr / col for everything else; a group of G lanes per row (8 for the short
-//   rows of P1 / Q1 / volume patterns, a wave for the hexahedral Q_p rows), shuffle reduction in a fixed order.
+//   Two theta modes, which differ in the staging and in the read of a matrix entry only:
+//   NC = 0 (apply_tile_kernel): one theta for all vectors, combined on the way into the LDS -- one image whatever
+//     n_comp, one LDS read per entry;
+//   NC >= 1 (apply_tile_multi_kernel, NC = n_comp): a theta per vector -- image q holds component q's values of the
+//     tile in the same layout at lds + q * I::BYTES / 8, and the combination happens at the read: NC LDS reads per
+//     entry, then the theta chain per vector.  NC * I::BYTES of LDS per wave: P1 19,456 B per image (NC <= 3:
+//     58,368 B, inside the 64 KB a launch gets without raising the kernel's dynamic-LDS attribute), Q1 40,960 B (NC = 1).
+// apply_csr_body -- plain CSR on row_ptr / col for everything else; a group of G lanes per row (8 for the short
+//   rows of P1 / Q1 / volume patterns, a wave for the hexahedral Q_p rows), shuffle reduction in a fixed order.  One
+//   theta (apply_csr_kernel): the matrix entry once per nonzero; a theta per vector (apply_csr_multi_kernel): the
+//   n_comp values loaded once, then a chain per vector; every n_comp <= HDD_MAX_COMP.
+// A theta per vector (hdd_operator_apply_multi, hdd_operator_solve_multi): y_v = (sum_q theta[v][q] A_q) x_v, the same
+//   affine components at several parameters, the value stream read once per group of NV vectors.  Both modes take the
+//   matrix entry from apply_entries, the one place where it is written: m = theta[0] a_0, m = fma(theta[q], a_q, m)
+//   for q = 1 .. n_comp - 1 in separate statements, then acc = fma(m, x, acc) -- so y_v, and the DOT partial sums on
+//   the same grid, are bit for bit those of the single-theta launch on (theta[v], x_v).  Entries of vectors >= nv are
+//   copies of vector 0's (never stored).
 // apply2_partial_kernel / apply2_final_kernel -- out[i][j] = v_i . w_j in two deterministic stages.
 // DOT variants (a square diagonal range: x and y share their numbering) also leave x_v . y_v behind, for the
 //   conjugate gradient iteration: every lane adds x_r y_r of its own rows over its tiles / rows in order, the
@@ -62,6 +76,12 @@ struct ApplyArgs {
   int32_t iteration;
 };
 
+// the arguments of the kernels with a theta per vector
+struct ApplyMultiArgs {
+  ApplyArgs a;                         // a.theta is not read
+  double theta[APPLY_NV][HDD_MAX_COMP];
+};
+
 // sizes of the tile kernel's LDS image: 16-byte chunks per lane (odd row blocks, P1: the image origin may lie one
 // value in front of the tile) and how many of them are loaded back to back
 template <int NB, int NF>
@@ -92,11 +112,46 @@ __device__ __forceinline__ int64_t apply_uni64(int64_t v)
 // whole to c ^ ((c >> 4) & 15), so the staging writes stay aligned and conflict-free.
 __device__ __forceinline__ int apply_swz(int p) { return p ^ (((p >> 5) & 15) << 1); }
 
-template <int NB, int NF, int NV, bool DOT = false>
-__global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
+// One matrix entry at NT thetas: m[t] = sum_q theta[t][q] comp(q), the n components read once.  The statements are
+// the contract (the build contracts within an expression only): a product, then one fma per further component.
+template <int NT, class Comp>
+__device__ __forceinline__ void apply_entries(double (&m)[NT], const double (*theta)[HDD_MAX_COMP], int n, Comp&& comp)
+{
+  {
+    const double w = comp(0);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) m[t] = theta[t][0] * w;
+  }
+  for (int q = 1; q < n; ++q) {
+    const double w = comp(q);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) m[t] = __builtin_fma(theta[t][q], w, m[t]);
+  }
+}
+
+// (sum_q theta_q A_q)[k] of the plan's theta, from the value arrays
+__device__ __forceinline__ double apply_entry(const ApplyArgs& a, int64_t k)
+{
+  double m[1];
+  apply_entries<1>(m, &a.theta, a.n_comp, [&](int q) { return a.vals[q][k]; });
+  return m[0];
+}
+
+// the sum of s over the wave, in every lane (the tree of every DOT variant)
+__device__ __forceinline__ double apply_wave_sum(double s)
+{
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) s += __shfl_xor(s, d, 64);
+  return s;
+}
+
+// The tile algorithm (header comment).  NC = 0: theta[0] for all vectors; NC >= 1: theta[v] for vector v, NC = n_comp.
+template <int NB, int NF, int NV, bool DOT, int NC>
+__device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double (*theta)[HDD_MAX_COMP], int64_t n_tiles)
 {
   using I = ApplyImage<NB, NF>;
-  constexpr int CH = I::CHUNKS, U = I::U;
+  constexpr int CH = I::CHUNKS, U = I::U, IMG = I::BYTES / 8;
+  constexpr int NT = NC ? NV : 1;   // thetas
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int lane = threadIdx.x;
   [[maybe_unused]] double dot[NV] = {};   // DOT: this lane's x_v . y_v over its elements, in tile order
@@ -105,8 +160,13 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
   const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
   const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
   __amdgpu_buffer_rsrc_t xr[NV];
+  [[maybe_unused]] double th[NT][HDD_MAX_COMP];   // NC >= 1: the thetas in registers (entries [.][< NC])
 #pragma unroll
-  for (int v = 0; v < NV; ++v) xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
+  for (int v = 0; v < NV; ++v) {
+    xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
+#pragma unroll
+    for (int q = 0; q < NC; ++q) th[v][q] = theta[v][q];
+  }
   for (int64_t t = r.t; t < r.t_end; t += r.t_step) {
     const int64_t t0 = a.e_begin + t * 64;
     const int64_t tend = t0 + 64 < a.e_end ? t0 + 64 : a.e_end;
@@ -121,38 +181,55 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
     const int tlen_al = int(tile_end - base_al);   // image length in values, from the aligned origin
     // the previous tile's image has been read by every lane
     lds_wave_sync();
-    // [stream the tile's values -> theta combination -> LDS image]; chunks beyond the tile read zero (range check)
+    // [stream the tile's values -> LDS image]; chunks beyond the tile read zero (range check)
     const uint32_t vbytes = tile_end > base_al ? uint32_t(tlen_al) * 8u : 0u;
+    if constexpr (NC == 0) {   // the theta combination on the way: one image
 #pragma unroll 1
-    for (int k0 = 0; k0 < CH; k0 += U) {
-      if (k0 * 128 >= tlen_al) break;
-      dvec2 v[U];
-      {
-        const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[0] + base_al, vbytes);
-        const double th = a.theta[0];
+      for (int k0 = 0; k0 < CH; k0 += U) {
+        if (k0 * 128 >= tlen_al) break;
+        dvec2 v[U];
+        {
+          const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[0] + base_al, vbytes);
+          const double th0 = theta[0][0];
 #pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = th * ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
-      }
-#pragma unroll 1
-      for (int q = 1; q < a.n_comp; ++q) {
-        const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
-        const double th = a.theta[q];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-          const dvec2 w = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
-          v[u].x = __builtin_fma(th, w.x, v[u].x);
-          v[u].y = __builtin_fma(th, w.y, v[u].y);
+          for (int u = 0; u < U; ++u) v[u] = th0 * ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
         }
-      }
+#pragma unroll 1
+        for (int q = 1; q < a.n_comp; ++q) {
+          const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
+          const double thq = theta[0][q];
 #pragma unroll
-      for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
-    }
-    // an odd image length: the last value has no whole 16-byte chunk inside the tile's range
-    if ((tlen_al & 1) && lane == 0) {
-      const uint32_t o8 = uint32_t(tlen_al - 1) * 8u;
-      double s = a.theta[0] * ld64f(apply_rsrc(a.vals[0] + base_al, vbytes), o8);
-      for (int q = 1; q < a.n_comp; ++q) s = __builtin_fma(a.theta[q], ld64f(apply_rsrc(a.vals[q] + base_al, vbytes), o8), s);
-      lds[apply_swz(tlen_al - 1)] = s;
+          for (int u = 0; u < U; ++u) {
+            const dvec2 w = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
+            v[u].x = __builtin_fma(thq, w.x, v[u].x);
+            v[u].y = __builtin_fma(thq, w.y, v[u].y);
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
+      }
+      // an odd image length: the last value has no whole 16-byte chunk inside the tile's range
+      if ((tlen_al & 1) && lane == 0) {
+        const uint32_t o8 = uint32_t(tlen_al - 1) * 8u;
+        double s[1];
+        apply_entries<1>(s, theta, a.n_comp, [&](int q) { return ld64f(apply_rsrc(a.vals[q] + base_al, vbytes), o8); });
+        lds[apply_swz(tlen_al - 1)] = s[0];
+      }
+    } else {   // a component at a time -> its image
+#pragma unroll
+      for (int q = 0; q < NC; ++q) {
+        const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
+#pragma unroll 1
+        for (int k0 = 0; k0 < CH; k0 += U) {
+          if (k0 * 128 >= tlen_al) break;
+          dvec2 v[U];
+#pragma unroll
+          for (int u = 0; u < U; ++u) v[u] = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
+#pragma unroll
+          for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + q * IMG + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
+        }
+        if ((tlen_al & 1) && lane == 0) lds[q * IMG + apply_swz(tlen_al - 1)] = ld64f(vr, uint32_t(tlen_al - 1) * 8u);
+      }
     }
     lds_wave_sync();
     // [lane = element: row block from the image, block columns from the neighbours, x gathered per block]
@@ -199,215 +276,17 @@ __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64
       for (int i = 0; i < NB; ++i)
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-          const double m = lds[apply_swz(off + i * rl + b * NB + j)];
-#pragma unroll
-          for (int v = 0; v < NV; ++v) acc[v][i] = __builtin_fma(m, xv[v][j], acc[v][i]);
-        }
-    }
-    double* yo = a.y + (e - a.e_begin) * NB;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-      if (v < a.nv)
-#pragma unroll
-        for (int i = 0; i < NB; ++i) yo[v * a.ldy + i] = acc[v][i];
-    if constexpr (DOT)
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-#pragma unroll
-        for (int i = 0; i < NB; ++i) dot[v] = __builtin_fma(xown[v][i], acc[v][i], dot[v]);
-  }
-  if constexpr (DOT) {   // every lane is back here, whatever its tiles were
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
-      if (lane == 0 && v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = dot[v];
-    }
-  }
-}
-
-// G lanes per row, 256 / G rows per workgroup pass
-template <int G, int NV, bool DOT = false>
-__global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
-{
-  [[maybe_unused]] double dot[NV] = {};   // DOT: the group leaders' x_r y_r over their rows, in row order
-  if constexpr (DOT)
-    if (*a.done_at <= a.iteration) return;   // (uniform)
-  const int gl = threadIdx.x % G;
-  const int64_t n_rows = a.row_end - a.row_begin;
-  const int64_t stride = int64_t(gridDim.x) * (256 / G);
-  for (int64_t rr = int64_t(blockIdx.x) * (256 / G) + threadIdx.x / G; rr < n_rows; rr += stride) {
-    int64_t k0 = a.row_ptr[a.row_begin + rr], k1 = a.row_ptr[a.row_begin + rr + 1];
-    k0 = k0 < 0 ? 0 : k0;
-    k1 = k1 > a.nnz ? a.nnz : k1;
-    double acc[NV];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.0;
-    for (int64_t k = k0 + gl; k < k1; k += G) {
-      const int64_t c = a.col[k];
-      if (c < a.col_begin || c >= a.col_end) continue;   // skipped, not multiplied by zero
-      double m = a.theta[0] * a.vals[0][k];
-      for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
-      const double* xc = a.x + (c - a.col_begin);
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        if (v < a.nv) acc[v] = __builtin_fma(m, xc[v * a.ldx], acc[v]);
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-      for (int s = G / 2; s > 0; s >>= 1) acc[v] += __shfl_xor(acc[v], s, G);
-    if (gl == 0)
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
-    if constexpr (DOT)
-      if (gl == 0)   // square diagonal range: row rr is column rr
-#pragma unroll
-        for (int v = 0; v < NV; ++v)
-          if (v < a.nv) dot[v] = __builtin_fma(a.x[v * a.ldx + rr], acc[v], dot[v]);
-  }
-  if constexpr (DOT) {
-    __shared__ double red[NV][4];
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
-      if ((threadIdx.x & 63) == 0) red[v][threadIdx.x >> 6] = dot[v];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0)
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-        if (v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
-  }
-}
-
-// ---- a theta per vector (hdd_operator_apply_multi, hdd_operator_solve_multi) -------------------------------------
-// y_v = (sum_q theta[v][q] A_q) x_v: the same affine components at several parameters, the value stream read once
-// per group of NV vectors.  Vector v keeps the arithmetic of the single-theta kernels on (theta[v], x_v): the matrix
-// entry m = theta[v][0] a_0, m = fma(theta[v][q], a_q, m) for q = 1 .. n_comp - 1 in separate statements, then
-// acc = fma(m, x, acc) -- so y_v, and the DOT partial sums on the same grid, are bit for bit those of the
-// single-theta launch.  Entries of vectors >= nv are copies of vector 0's (never stored).
-struct ApplyMultiArgs {
-  ApplyArgs a;                         // a.theta is not read
-  double theta[APPLY_NV][HDD_MAX_COMP];
-};
-
-// apply_tile_kernel with NC (= n_comp, compile time) component images in the LDS instead of the one theta-combined
-// image: image q holds component q's values of the tile in ApplyImage's layout (apply_swz) at lds + q * I::BYTES / 8,
-// and the combination happens at the read: per matrix entry NC LDS reads, then per vector the theta chain and one FMA.
-// Tile order, lane -> element, the x gathers, xown / dot, the shuffle trees and the partials are apply_tile_kernel's;
-// it runs on the same grids.  NC * I::BYTES of LDS per wave: P1 19,456 B per image (NC <= 3: 58,368 B, inside the
-// 64 KB a launch gets without raising the kernel's dynamic-LDS attribute), Q1 40,960 B (NC = 1).
-template <int NB, int NF, int NV, bool DOT, int NC>
-__global__ void __launch_bounds__(64) apply_tile_multi_kernel(const ApplyMultiArgs ma, int64_t n_tiles)
-{
-  using I = ApplyImage<NB, NF>;
-  constexpr int CH = I::CHUNKS, U = I::U, IMG = I::BYTES / 8;
-  static_assert(NV <= APPLY_NV && NC >= 1 && NC <= HDD_MAX_COMP, "theta[APPLY_NV][HDD_MAX_COMP]");
-  extern __shared__ __attribute__((aligned(16))) double lds[];
-  const ApplyArgs& a = ma.a;
-  const int lane = threadIdx.x;
-  [[maybe_unused]] double dot[NV] = {};   // DOT: this lane's x_v . y_v over its elements, in tile order
-  if constexpr (DOT)
-    if (*a.done_at <= a.iteration) return;   // (wave-uniform)
-  const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
-  const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
-  __amdgpu_buffer_rsrc_t xr[NV];
-  double th[NV][NC];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
-#pragma unroll
-    for (int q = 0; q < NC; ++q) th[v][q] = ma.theta[v][q];
-  }
-  for (int64_t t = r.t; t < r.t_end; t += r.t_step) {
-    const int64_t t0 = a.e_begin + t * 64;
-    const int64_t tend = t0 + 64 < a.e_end ? t0 + 64 : a.e_end;
-    const bool active = t0 + lane < tend;
-    const int64_t e = active ? t0 + lane : t0;
-    int nbr[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) nbr[f] = a.nbrs[f * a.n_local + e];
-    const int64_t base = apply_uni64(a.elem_ptr[t0 - a.own_begin]);
-    const int64_t tile_end = apply_uni64(a.elem_ptr[tend - a.own_begin]);
-    const int64_t base_al = base & ~int64_t(1);
-    const int tlen_al = int(tile_end - base_al);   // image length in values, from the aligned origin
-    // the previous tile's images have been read by every lane
-    lds_wave_sync();
-    // [stream the tile's values, a component at a time -> its LDS image]; chunks beyond the tile read zero
-    const uint32_t vbytes = tile_end > base_al ? uint32_t(tlen_al) * 8u : 0u;
-#pragma unroll
-    for (int q = 0; q < NC; ++q) {
-      const __amdgpu_buffer_rsrc_t vr = apply_rsrc(a.vals[q] + base_al, vbytes);
-#pragma unroll 1
-      for (int k0 = 0; k0 < CH; k0 += U) {
-        if (k0 * 128 >= tlen_al) break;
-        dvec2 v[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) v[u] = ld128f(vr, uint32_t(lane + 64 * (k0 + u)) * 16u);
-#pragma unroll
-        for (int u = 0; u < U; ++u) *reinterpret_cast<dvec2*>(lds + q * IMG + apply_swz(2 * (lane + 64 * (k0 + u)))) = v[u];
-      }
-      // an odd image length: the last value has no whole 16-byte chunk inside the tile's range
-      if ((tlen_al & 1) && lane == 0) lds[q * IMG + apply_swz(tlen_al - 1)] = ld64f(vr, uint32_t(tlen_al - 1) * 8u);
-    }
-    lds_wave_sync();
-    // [lane = element: row block from the images, block columns from the neighbours, x gathered per block]
-    int nint = 0;
-#pragma unroll
-    for (int f = 0; f < NF; ++f) nint += nbr[f] >= 0;
-    const int off = tile_offset<NB>(nint, active) + int(base - base_al);
-    if (!active) continue;
-    int id[NF + 1];
-    id[0] = int(e);
-#pragma unroll
-    for (int f = 0; f < NF; ++f) id[f + 1] = nbr[f] >= 0 ? nbr[f] : 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < NF; ++i)
-#pragma unroll
-      for (int j = 0; j < NF - i; ++j) {
-        const int lo = id[j] < id[j + 1] ? id[j] : id[j + 1], hi = id[j] < id[j + 1] ? id[j + 1] : id[j];
-        id[j] = lo;
-        id[j + 1] = hi;
-      }
-    const int rl = NB * (nint + 1);   // row length
-    double acc[NV][NB];
-    [[maybe_unused]] double xown[NV][NB] = {};
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-      for (int i = 0; i < NB; ++i) acc[v][i] = 0.0;
-#pragma unroll
-    for (int b = 0; b <= NF; ++b) {
-      if (b > nint || id[b] < a.ce_begin || id[b] >= a.ce_end) continue;   // skipped, not multiplied by zero
-      const uint32_t xo = uint32_t(id[b] - int(a.ce_begin)) * uint32_t(NB * 8);
-      double xv[NV][NB];
-#pragma unroll
-      for (int v = 0; v < NV; ++v)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) xv[v][j] = v < a.nv ? ld64f(xr[v], xo + 8u * j) : 0.0;
-      if constexpr (DOT)   // the element's own block is one of the gathered ones: these are its rows of x
-        if (id[b] == int(e))
-#pragma unroll
-          for (int v = 0; v < NV; ++v)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) xown[v][j] = xv[v][j];
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
           const int p = apply_swz(off + i * rl + b * NB + j);
-          double c[NC];
+          // the entry: the combined image's, or per vector from the component images
+          [[maybe_unused]] double c[NC ? NC : 1];
+          if constexpr (NC == 0) c[0] = lds[p];
 #pragma unroll
           for (int q = 0; q < NC; ++q) c[q] = lds[q * IMG + p];
 #pragma unroll
           for (int v = 0; v < NV; ++v) {
-            double m = th[v][0] * c[0];
-#pragma unroll
-            for (int q = 1; q < NC; ++q) m = __builtin_fma(th[v][q], c[q], m);
-            acc[v][i] = __builtin_fma(m, xv[v][j], acc[v][i]);
+            double m[1] = {c[0]};
+            if constexpr (NC > 0) apply_entries<1>(m, th + v, NC, [&](int q) { return c[q]; });
+            acc[v][i] = __builtin_fma(m[0], xv[v][j], acc[v][i]);
           }
         }
     }
@@ -426,20 +305,30 @@ __global__ void __launch_bounds__(64) apply_tile_multi_kernel(const ApplyMultiAr
   if constexpr (DOT) {   // every lane is back here, whatever its tiles were
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      dot[v] = apply_wave_sum(dot[v]);
       if (lane == 0 && v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = dot[v];
     }
   }
 }
 
-// apply_csr_kernel with the theta chain per vector and nonzero: the n_comp values are loaded once, then NV chains.
-// Row -> group, shuffle order and partials are apply_csr_kernel's; every n_comp <= HDD_MAX_COMP.
-template <int G, int NV, bool DOT = false>
-__global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiArgs ma)
+template <int NB, int NF, int NV, bool DOT = false>
+__global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
 {
-  static_assert(NV <= APPLY_NV, "theta[APPLY_NV][HDD_MAX_COMP]");
-  const ApplyArgs& a = ma.a;
+  apply_tile_body<NB, NF, NV, DOT, 0>(a, &a.theta, n_tiles);
+}
+
+template <int NB, int NF, int NV, bool DOT, int NC>
+__global__ void __launch_bounds__(64) apply_tile_multi_kernel(const ApplyMultiArgs ma, int64_t n_tiles)
+{
+  static_assert(NV <= APPLY_NV && NC >= 1 && NC <= HDD_MAX_COMP, "theta[APPLY_NV][HDD_MAX_COMP]");
+  apply_tile_body<NB, NF, NV, DOT, NC>(ma.a, ma.theta, n_tiles);
+}
+
+// The CSR algorithm: G lanes per row, 256 / G rows per workgroup pass.  NT = 1: theta[0] for all vectors; NT = NV:
+// theta[v] for vector v.
+template <int G, int NV, bool DOT, int NT>
+__device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const double (*theta)[HDD_MAX_COMP])
+{
   [[maybe_unused]] double dot[NV] = {};   // DOT: the group leaders' x_r y_r over their rows, in row order
   if constexpr (DOT)
     if (*a.done_at <= a.iteration) return;   // (uniform)
@@ -456,21 +345,12 @@ __global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiAr
     for (int64_t k = k0 + gl; k < k1; k += G) {
       const int64_t c = a.col[k];
       if (c < a.col_begin || c >= a.col_end) continue;   // skipped, not multiplied by zero
-      double m[NV];
-      {
-        const double w = a.vals[0][k];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) m[v] = ma.theta[v][0] * w;
-      }
-      for (int q = 1; q < a.n_comp; ++q) {
-        const double w = a.vals[q][k];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) m[v] = __builtin_fma(ma.theta[v][q], w, m[v]);
-      }
+      double m[NT];
+      apply_entries<NT>(m, theta, a.n_comp, [&](int q) { return a.vals[q][k]; });
       const double* xc = a.x + (c - a.col_begin);
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        if (v < a.nv) acc[v] = __builtin_fma(m[v], xc[v * a.ldx], acc[v]);
+        if (v < a.nv) acc[v] = __builtin_fma(m[NT == 1 ? 0 : v], xc[v * a.ldx], acc[v]);
     }
 #pragma unroll
     for (int v = 0; v < NV; ++v)
@@ -490,8 +370,7 @@ __global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiAr
     __shared__ double red[NV][4];
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-#pragma unroll
-      for (int d = 32; d > 0; d >>= 1) dot[v] += __shfl_xor(dot[v], d, 64);
+      dot[v] = apply_wave_sum(dot[v]);
       if ((threadIdx.x & 63) == 0) red[v][threadIdx.x >> 6] = dot[v];
     }
     __syncthreads();
@@ -500,6 +379,19 @@ __global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiAr
       for (int v = 0; v < NV; ++v)
         if (v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
   }
+}
+
+template <int G, int NV, bool DOT = false>
+__global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
+{
+  apply_csr_body<G, NV, DOT, 1>(a, &a.theta);
+}
+
+template <int G, int NV, bool DOT = false>
+__global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiArgs ma)
+{
+  static_assert(NV <= APPLY_NV, "theta[APPLY_NV][HDD_MAX_COMP]");
+  apply_csr_body<G, NV, DOT, NV>(ma.a, ma.theta);
 }
 
 // apply2, stage 1: partial[block][i * HDD_MAX_VEC + j] = sum over the block's rows of v_i[r] w_j[r] (fixed row ->

@@ -1,9 +1,12 @@
 // dune-hdd_amd/csrc/kernels/apply_plan.hh -- the checked plan of an operator application (internal): what
-// hdd_operator_apply / _apply2 (abi_apply.hip, which defines these functions) and hdd_operator_solve (abi_solve.hip)
-// share, so that the operator arguments are checked and dispatched in one place.
+// hdd_operator_apply / _apply_multi / _apply2 (abi_apply.hip, which defines the functions declared here) and
+// hdd_operator_solve[_batched / _multi] (abi_solve.hip) share, so that the operator arguments are checked in one
+// place (plan_apply) and every apply kernel is launched from one place (launch_apply).
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <string>
+#include <type_traits>
 
 #include "abi_common.hh"
 #include "apply_kernels.hh"
@@ -17,49 +20,94 @@ struct ApplyPlan {
   bool tile;
   int nb, nf;        // tile path
   bool short_rows;   // generic path: a group of 8 lanes per row instead of a wave
+  int64_t rows() const { return a.row_end - a.row_begin; }
+  int64_t n_tiles() const { return (a.e_end - a.e_begin + 63) / 64; }
+  int image_bytes() const { return nb == 3 ? dev::ApplyImage<3, 3>::BYTES : dev::ApplyImage<4, 4>::BYTES; }
+};
+
+// a theta per vector: theta[j * ldt + q] for vector j (theta NULL: ones)
+struct ApplyThetas {
+  const double* theta;
+  int64_t ldt;
 };
 
 // Every check of hdd_operator_apply's operator arguments (no device call, nothing dereferenced but host structs);
-// fills the plan except x / y.
+// fills the plan except x / y.  per_vector (hdd_operator_apply_multi / _solve_multi; theta is then not read: ones):
+// the tile path only where the n_comp component images fit the LDS a launch gets by default (P1: n_comp <= 3, Q1:
+// n_comp == 1); what does not fit takes the CSR kernel, whose arrays the pattern must then have.
 int plan_apply(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
-               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P);
-
-// the launches of a checked plan: the values are read once per group of APPLY_NV vectors
-int run_apply(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* d_x, int64_t ldx, double* d_y, int64_t ldy,
-              int32_t n_vec, void* stream);
-
-// A theta per vector (hdd_operator_apply_multi / _solve_multi): the plan of (theta row 0 or ones), then the tile path
-// only where the n_comp component images fit the LDS a launch gets by default (P1: n_comp <= 3, Q1: n_comp == 1);
-// what does not fit takes the CSR kernel, whose arrays the pattern must then have.
-int plan_apply_multi(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
-                     int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P);
-inline bool apply_multi_tile_fits(int nb, int n_comp) { return nb == 3 ? n_comp <= 3 : n_comp == 1; }
+               int32_t n_comp, const double* theta, const hdd_block_range* range, ApplyPlan& P, bool per_vector = false);
 
 // the kernel arguments of one group: vector v < nv gets theta[(v0 + v) * ldt + q] (theta NULL: ones), the others
 // copies of the group's first
-void apply_multi_thetas(dev::ApplyMultiArgs& ma, const double* theta, int64_t ldt, int v0);
+void apply_multi_thetas(dev::ApplyMultiArgs& ma, const ApplyThetas& T, int v0);
 
-// the launches of a checked multi plan, the values read once per group of APPLY_NV vectors
-int run_apply_multi(const char* who, hdd_ctx* ctx, ApplyPlan& P, const double* theta, int64_t ldt, const double* d_x, int64_t ldx,
-                    double* d_y, int64_t ldy, int32_t n_vec, void* stream);
+// the launches of a checked plan: the values are read once per group of APPLY_NV vectors.  T NULL: the plan's theta
+// for every vector.
+int run_apply(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const ApplyThetas* T, const double* d_x, int64_t ldx,
+              double* d_y, int64_t ldy, int32_t n_vec, void* stream);
 
-// workgroups of the tile kernel: as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB); tile_range wants
-// a multiple of 8 workgroups
-template <int NB, int NF>
-inline int64_t apply_tile_grid(const hdd_ctx* ctx, int64_t n_tiles)
+// "apply_tile_kernel<3, 3, 4>", "apply_csr_multi_kernel<8, 4, dot>", ...: the instantiation launch_apply<nv, dot>
+// takes for the plan, appended to out
+void apply_kernel_name(std::string& out, const ApplyPlan& P, bool per_vector, int nv, bool dot);
+
+// Workgroups of a plain launch.  Tile kernel: as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB),
+// tile_range wants a multiple of 8 workgroups; CSR kernel: 256 / G rows per workgroup pass.
+inline int64_t apply_grid(const hdd_ctx* ctx, const ApplyPlan& P)
 {
-  using I = dev::ApplyImage<NB, NF>;
-  const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / I::BYTES));
-  const int64_t G = std::max<int64_t>(8, (int64_t(ctx->n_cu) * per_cu) & ~int64_t(7));
-  return G >= n_tiles ? n_tiles : G;
+  if (P.tile) {
+    const int64_t per_cu = std::max<int64_t>(1, std::min<int64_t>(8, (160 * 1024) / P.image_bytes()));
+    const int64_t G = std::max<int64_t>(8, (int64_t(ctx->n_cu) * per_cu) & ~int64_t(7));
+    return G >= P.n_tiles() ? P.n_tiles() : G;
+  }
+  const int64_t per_wg = 256 / (P.short_rows ? 8 : 64);
+  return std::min<int64_t>((P.rows() + per_wg - 1) / per_wg, 256 * 64);
 }
 
-// workgroups of the CSR kernel with G lanes per row
-template <int G>
-inline int64_t apply_csr_grid(int64_t n_rows)
+// workgroups of a DOT launch (= partial sums per vector it writes, at most max_parts)
+inline int64_t dot_grid(const hdd_ctx* ctx, const ApplyPlan& P, int64_t max_parts)
 {
-  const int64_t per_wg = 256 / G;
-  return std::min<int64_t>((n_rows + per_wg - 1) / per_wg, 256 * 64);
+  const int64_t G = apply_grid(ctx, P);
+  if (!P.tile) return std::min<int64_t>(G, 2048);
+  return G > max_parts ? max_parts & ~int64_t(7) : G;   // tile_range: a multiple of 8 below the tile count
+}
+
+// One launch of a checked plan on `grid` workgroups for args.nv <= NV vectors: tile NB 3 / 4 (times the component
+// images) or CSR 8 / 64.  Args is dev::ApplyArgs (the plan's theta) or dev::ApplyMultiArgs (a theta per vector).
+template <int NV, bool DOT, class Args>
+hipError_t launch_apply(const ApplyPlan& P, const Args& args, int64_t grid, hipStream_t s)
+{
+  constexpr bool PER_VECTOR = std::is_same_v<Args, dev::ApplyMultiArgs>;
+  const dim3 g{unsigned(grid)};
+  auto tile = [&](auto nb, auto nc) {
+    constexpr int NB = decltype(nb)::value, NC = decltype(nc)::value;
+    using I = dev::ApplyImage<NB, NB>;   // P1: 3 values, 3 faces; Q1: 4 and 4
+    static_assert(std::max(NC, 1) * I::BYTES <= 64 * 1024, "the dynamic LDS a launch gets without raising the kernel's attribute");
+    if constexpr (PER_VECTOR)
+      hipLaunchKernelGGL((dev::apply_tile_multi_kernel<NB, NB, NV, DOT, NC>), g, dim3(64), NC * I::BYTES, s, args, P.n_tiles());
+    else
+      hipLaunchKernelGGL((dev::apply_tile_kernel<NB, NB, NV, DOT>), g, dim3(64), I::BYTES, s, args, P.n_tiles());
+  };
+  auto csr = [&](auto lanes) {
+    constexpr int G = decltype(lanes)::value;
+    if constexpr (PER_VECTOR) hipLaunchKernelGGL((dev::apply_csr_multi_kernel<G, NV, DOT>), g, dim3(256), 0, s, args);
+    else hipLaunchKernelGGL((dev::apply_csr_kernel<G, NV, DOT>), g, dim3(256), 0, s, args);
+  };
+  using std::integral_constant;
+  constexpr integral_constant<int, PER_VECTOR ? 1 : 0> one{};   // NC: the plan's theta has the combined image (0)
+  int images = 1;   // component images of a P1 tile (plan_apply: at most 3; Q1: 1)
+  if constexpr (PER_VECTOR) images = args.a.n_comp;
+  if (P.tile && P.nb == 3) {
+    if (images == 1) tile(integral_constant<int, 3>{}, one);
+    else if (images == 2) tile(integral_constant<int, 3>{}, integral_constant<int, 2>{});
+    else tile(integral_constant<int, 3>{}, integral_constant<int, 3>{});
+  } else if (P.tile)
+    tile(integral_constant<int, 4>{}, one);
+  else if (P.short_rows)
+    csr(integral_constant<int, 8>{});
+  else
+    csr(integral_constant<int, 64>{});
+  return hipGetLastError();
 }
 
 }  // namespace abi

@@ -211,9 +211,7 @@ __global__ void __launch_bounds__(256) solve_dinv_tile_kernel(const ApplyArgs a,
       for (int c = 0; c < NB; ++c) {
         int64_t k = base + r * rl + c;
         k = k < 0 ? 0 : (k >= a.nnz ? a.nnz - 1 : k);   // an index the mesh got wrong stays inside the arrays
-        double m = a.theta[0] * a.vals[0][k];
-        for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
-        D[r][c] = m;
+        D[r][c] = apply_entry(a, k);
       }
     if (!solve_invert<NB>(D, dinv + i * solve_packed<NB>())) bad += 1.0;
   }
@@ -241,8 +239,7 @@ __global__ void __launch_bounds__(256) solve_dinv_csr_kernel(const ApplyArgs a, 
       for (int64_t k = k0; k < k1; ++k) {
         const int64_t c = int64_t(a.col[k]) - r0;
         if (c < 0 || c >= BS) continue;
-        double m = a.theta[0] * a.vals[0][k];
-        for (int q = 1; q < a.n_comp; ++q) m = __builtin_fma(a.theta[q], a.vals[q][k], m);
+        const double m = apply_entry(a, k);
 #pragma unroll
         for (int cc = 0; cc < BS; ++cc)
           if (cc == c) D[r][cc] += m;

@@ -896,6 +896,23 @@ def _apply_operands(dpattern, vals, theta, dmesh, block, grid):
     return vals, n, ptrs, th, rng, rows, cols, dmesh
 
 
+def _apply_vectors(who, x_name, X, out, rows, cols, stream, after_x=None):
+    """what apply and apply_multi share: X [n_vec, cols] and out [n_vec, rows] (None: made here) are float64 with unit
+    inner stride; their leading dimensions and the stream.  after_x(n_vec) runs between the two checks, its result
+    is the last entry of (n_vec, ldx, out, ldy, stream, result)."""
+    torch = _torch()
+    if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1 or X.shape[1] != cols:
+        raise HddError("%s: %s must be float64 [n_vec, %d] with unit inner stride" % (who, x_name, cols))
+    n_vec = X.shape[0]
+    extra = after_x(n_vec) if after_x else None
+    if out is None:
+        out = torch.empty((n_vec, rows), dtype=torch.float64, device=X.device)
+    if out.dim() != 2 or out.dtype != torch.float64 or out.stride(1) != 1 or out.shape != (n_vec, rows):
+        raise HddError("%s: out must be float64 [n_vec, %d] with unit inner stride" % (who, rows))
+    s = stream if stream is not None else torch.cuda.current_stream(X.device).cuda_stream
+    return (n_vec, X.stride(0) if n_vec > 1 else max(cols, 1), out, out.stride(0) if n_vec > 1 else max(rows, 1), s, extra)
+
+
 def apply(ctx, dpattern, vals, x, theta=None, dmesh=None, block=None, out=None, stream=None, grid=None):
     """hdd_operator_apply: y = (sum_q theta[q] A_q) x on the device, A_q = vals[q] on dpattern (theta None: all
     ones) -- pyMOR's apply on the affinely decomposed operator at a parameter without writing A(mu).  x: [n] or
@@ -903,20 +920,12 @@ def apply(ctx, dpattern, vals, x, theta=None, dmesh=None, block=None, out=None, 
     whose SWIPDG face pattern dpattern is -> the tile kernel (P1 / Q1, whole-grid view); None -> the CSR kernel.
     block=(ss, nn): the BlockSWIPDG local / coupling operator (rows of ss, columns of nn; x in nn's numbering),
     applied on the global arrays without extraction."""
-    torch = _torch()
     vals, n, ptrs, th, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, theta, dmesh, block, grid)
     x2 = x if x.dim() == 2 else x.reshape(1, -1)
-    if x2.dtype != torch.float64 or x2.stride(1) != 1 or x2.shape[1] != cols:
-        raise HddError("apply: x must be float64 [n_vec, %d] with unit inner stride" % cols)
-    n_vec = x2.shape[0]
-    ldx = x2.stride(0) if n_vec > 1 else max(cols, 1)
+    y2 = out if out is None or out.dim() == 2 else out.reshape(1, -1)
+    n_vec, ldx, y2, ldy, s, _ = _apply_vectors("apply", "x", x2, y2, rows, cols, stream)
     if out is None:
-        out = torch.empty((n_vec, rows), dtype=torch.float64, device=x.device)
-    y2 = out if out.dim() == 2 else out.reshape(1, -1)
-    if y2.dtype != torch.float64 or y2.stride(1) != 1 or y2.shape != (n_vec, rows):
-        raise HddError("apply: out must be float64 [n_vec, %d] with unit inner stride" % rows)
-    ldy = y2.stride(0) if n_vec > 1 else max(rows, 1)
-    s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+        out = y2
     _check(lib().hdd_operator_apply(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
                                     n, _p(th), None if rng is None else C.addressof(rng), x2.data_ptr(), ldx,
                                     y2.data_ptr(), ldy, n_vec, C.c_void_p(s)), "hdd_operator_apply")
@@ -1058,19 +1067,9 @@ def apply_multi(ctx, dpattern, vals, X, thetas, dmesh=None, block=None, out=None
     MAX_VEC; thetas: host [n_vec, n_comp] (None: all ones).  Every other argument is apply()'s.  Row j is bit for bit
     apply(..., X[j], theta=thetas[j]) on the same path; the tile kernel takes P1 with at most three and Q1 with one
     value array, everything else the CSR kernel (then the bits of apply() with dmesh=None)."""
-    torch = _torch()
     vals, n, ptrs, _, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, None, dmesh, block, grid)
-    if X.dim() != 2 or X.dtype != torch.float64 or X.stride(1) != 1 or X.shape[1] != cols:
-        raise HddError("apply_multi: X must be float64 [n_vec, %d] with unit inner stride" % cols)
-    n_vec = X.shape[0]
-    th = _thetas("apply_multi", thetas, n_vec, n)
-    ldx = X.stride(0) if n_vec > 1 else max(cols, 1)
-    if out is None:
-        out = torch.empty((n_vec, rows), dtype=torch.float64, device=X.device)
-    if out.dim() != 2 or out.dtype != torch.float64 or out.stride(1) != 1 or out.shape != (n_vec, rows):
-        raise HddError("apply_multi: out must be float64 [n_vec, %d] with unit inner stride" % rows)
-    ldy = out.stride(0) if n_vec > 1 else max(rows, 1)
-    s = stream if stream is not None else torch.cuda.current_stream(X.device).cuda_stream
+    n_vec, ldx, out, ldy, s, th = _apply_vectors("apply_multi", "X", X, out, rows, cols, stream,
+                                                 lambda n_vec: _thetas("apply_multi", thetas, n_vec, n))
     _check(lib().hdd_operator_apply_multi(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t),
                                           ptrs, n, _p(th), n, None if rng is None else C.addressof(rng), X.data_ptr(), ldx,
                                           out.data_ptr(), ldy, n_vec, C.c_void_p(s)), "hdd_operator_apply_multi")

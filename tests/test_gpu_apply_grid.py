@@ -26,7 +26,7 @@ H = pytest.importorskip("hdd_amd")
 sp = pytest.importorskip("scipy.sparse")
 pytestmark = pytest.mark.gpu
 
-CSR_GRID_CAP = 16384      # apply_csr_grid: workgroups of a plain CSR launch
+CSR_GRID_CAP = 16384      # apply_grid: workgroups of a plain CSR launch
 APPLY2_BLOCKS = 512       # apply_kernels.hh
 HEX_N = (24, 20, 18)
 # penalty factor per case (H.params(8 s, 14 s)); 1: the reference's penalties.  test_gpu_solve_grid.py needs positive
@@ -45,7 +45,7 @@ def n_cu():
 
 
 def tile_grid(per_cu, n_tiles=None):
-    """apply_tile_grid: workgroups of the tile kernel (per_cu 8 for P1, 4 for Q1)"""
+    """apply_grid: workgroups of the tile kernel (per_cu 8 for P1, 4 for Q1)"""
     G = max(8, (n_cu() * per_cu) & ~7)
     return G if n_tiles is None else min(G, n_tiles)
 
