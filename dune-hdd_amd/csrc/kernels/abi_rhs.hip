@@ -147,6 +147,13 @@ extern "C" int hdd_product_assemble(hdd_ctx* ctx, const hdd_mesh* m, int32_t pro
   if (int rc = check_degree(who, m, &deg)) return rc;
   const int nb = mesh_nb(m->elem_type, deg);
   if (int rc = check_pattern_rows(who, pattern, nb, m)) return rc;
+  // the element-local kinds write nb values per row, the penalty nb per row and (own + interior face) block: what the
+  // host can tell from nnz alone (the penalty's block count per row lives in the device arrays)
+  const int64_t nnz_local = int64_t(nb) * nb * (m->own_end - m->own_begin);
+  if (product != HDD_PRODUCT_PENALTY && pattern->nnz != nnz_local)
+    return fail(HDD_ERR_INVALID, who, "element-local products need the volume pattern (nnz = nb^2 * owned elements)");
+  if (product == HDD_PRODUCT_PENALTY && pattern->nnz < nnz_local)
+    return fail(HDD_ERR_INVALID, who, "penalty pattern smaller than its diagonal blocks");
   ProductArgs a{};
   a.elem_type = m->elem_type;
   a.degree = deg;

@@ -364,7 +364,12 @@ int hdd_swipdg_rhs(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_scalar_fn* forc
  *   hdd_dg_pattern_fill with n_faces = 0 (row length nb);
  *   HDD_PRODUCT_PENALTY (kappa, tensor): the SWIPDG penalty terms sigma kappa^- kappa^+ gamma / |F|^beta on
  *   inner faces and the boundary penalty on Dirichlet faces; pattern = the SWIPDG pattern.
- * Writes d_vals[0..nnz) (every entry once). */
+ * Writes d_vals[0..nnz) (every entry once).
+ * Pattern check: the element-local kinds return HDD_ERR_INVALID unless pattern->nnz == nb * nb * owned elements
+ * (a SWIPDG pattern has the right row count but another layout); the penalty returns HDD_ERR_INVALID when
+ * pattern->nnz < nb * nb * owned elements.  Beyond that the host cannot verify a penalty pattern (its blocks per row
+ * are in the device arrays): the caller must pass the SWIPDG pattern of this mesh -- the kernel writes
+ * nb * (1 + interior faces) values per row, which a volume pattern's value array does not hold. */
 enum { HDD_PRODUCT_L2 = 0, HDD_PRODUCT_H1_SEMI = 1, HDD_PRODUCT_ELLIPTIC = 2, HDD_PRODUCT_BOUNDARY_L2 = 3,
        HDD_PRODUCT_PENALTY = 4 };
 int hdd_product_assemble(hdd_ctx* ctx, const hdd_mesh* mesh, int32_t product, const hdd_scalar_fn* kappa,
