@@ -1,5 +1,5 @@
-// dune-hdd_amd/csrc/kernels/abi_rhs.hip -- C ABI: right-hand side functionals and products (kernels: rhs.hip; P1 / Q1
-// products with piecewise-constant data: the persistent tile driver)
+// dune-hdd_amd/csrc/kernels/abi_rhs.hip -- C ABI: right-hand side functionals and products (kernels: rhs.hip and
+// products.hip; P1 / Q1 products with piecewise-constant data: the persistent tile driver)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +15,28 @@ static dev::KappaArg kap_arg(const hdd_scalar_fn* f)
 {
   if (!f) return dev::KappaArg{HDD_FN_CONST, 0, 0.0, 0.0, 0.0, 0.0, nullptr, nullptr, 0, 0};
   return dev::KappaArg{f->kind, f->order, f->c, f->b, f->kx, f->ky, f->per_elem, f->table, f->n_table, 0};
+}
+
+// the tensor fields of RhsArgs / ProductArgs
+template <class Args>
+static void set_tensor(Args& a, const hdd_tensor_fn* tensor)
+{
+  a.tkind = tensor ? tensor->kind : HDD_TENSOR_CONST;
+  for (int r = 0; r < 6; ++r) a.tc[r] = tensor ? tensor->c[r] : 0.0;
+  a.tper = tensor ? tensor->per_elem : nullptr;
+}
+
+// the 1D Gauss rule on [0, 1] that is exact to `order`: points into q[.][0], weights into q[.][wcol]; returns the
+// number of points, -1 beyond 16
+template <int W>
+static int gauss_rule_1d(int order, double (*q)[W], int wcol)
+{
+  const int n1 = std::max(1, (order + 2) / 2);
+  if (n1 > 16) return -1;
+  double s[16], w[16];
+  gauss_legendre01(n1, s, w);
+  for (int k = 0; k < n1; ++k) { q[k][0] = s[k]; q[k][wcol] = w[k]; }
+  return n1;
 }
 
 extern "C" int hdd_swipdg_rhs(hdd_ctx* ctx, const hdd_mesh* m, const hdd_scalar_fn* force, const hdd_scalar_fn* kappa,
@@ -54,9 +76,7 @@ extern "C" int hdd_swipdg_rhs(hdd_ctx* ctx, const hdd_mesh* m, const hdd_scalar_
     a.vxy = m->vertex_coords;
   }
   a.nbrs = m->neighbors;
-  a.tkind = tensor ? tensor->kind : HDD_TENSOR_CONST;
-  for (int r = 0; r < 6; ++r) a.tc[r] = tensor ? tensor->c[r] : 0.0;
-  a.tper = tensor ? tensor->per_elem : nullptr;
+  set_tensor(a, tensor);
   a.force = kap_arg(force);
   a.kappa = kap_arg(kappa);
   a.dirichlet = kap_arg(dirichlet);
@@ -165,9 +185,7 @@ extern "C" int hdd_product_assemble(hdd_ctx* ctx, const hdd_mesh* m, int32_t pro
   a.coords = m->coords;
   a.nbrs = m->neighbors;
   a.elem_ptr = pattern->elem_ptr;
-  a.tkind = tensor ? tensor->kind : HDD_TENSOR_CONST;
-  for (int r = 0; r < 6; ++r) a.tc[r] = tensor ? tensor->c[r] : 0.0;
-  a.tper = tensor ? tensor->per_elem : nullptr;
+  set_tensor(a, tensor);
   a.kappa = kap_arg(kappa);
   a.sigma_inner = p->sigma_inner;
   a.sigma_boundary = p->sigma_boundary;
@@ -178,25 +196,12 @@ extern "C" int hdd_product_assemble(hdd_ctx* ctx, const hdd_mesh* m, int32_t pro
   if (product <= HDD_PRODUCT_ELLIPTIC) {
     int order = product == HDD_PRODUCT_L2 ? 2 * deg + over : 2 * (deg - 1) + over;
     if (product == HDD_PRODUCT_ELLIPTIC) order += ko;
-    if (m->elem_type == HDD_SIMPLEX) {
-      a.nqv = simplex_rule(order, a.qv, 64);
-      if (a.nqv < 0) return set_error(HDD_ERR_UNSUPPORTED, "hdd_product_assemble: integration order too high");
-    } else {
-      const int n1 = std::max(1, (order + 2) / 2);
-      if (n1 > 16) return set_error(HDD_ERR_UNSUPPORTED, "hdd_product_assemble: integration order too high");
-      double s[16], w[16];
-      gauss_legendre01(n1, s, w);
-      for (int q = 0; q < n1; ++q) { a.qv[q][0] = s[q]; a.qv[q][3] = w[q]; }
-      a.nqv = n1;
-    }
+    a.nqv = m->elem_type == HDD_SIMPLEX ? simplex_rule(order, a.qv, 64) : gauss_rule_1d(order, a.qv, 3);
+    if (a.nqv < 0) return set_error(HDD_ERR_UNSUPPORTED, "hdd_product_assemble: integration order too high");
   } else {
     const int order = product == HDD_PRODUCT_BOUNDARY_L2 ? 2 * deg + over : ko + 2 * deg + over;
-    const int n1 = std::max(1, (order + 2) / 2);
-    if (n1 > 16) return set_error(HDD_ERR_UNSUPPORTED, "hdd_product_assemble: integration order too high");
-    double s[16], w[16];
-    gauss_legendre01(n1, s, w);
-    for (int q = 0; q < n1; ++q) { a.qf[q][0] = s[q]; a.qf[q][1] = w[q]; }
-    a.nq1f = n1;
+    a.nq1f = gauss_rule_1d(order, a.qf, 1);
+    if (a.nq1f < 0) return set_error(HDD_ERR_UNSUPPORTED, "hdd_product_assemble: integration order too high");
   }
   hipError_t e = hipSetDevice(ctx->device);
   if (e != hipSuccess) return hip_fail(e, "hdd_product_assemble: hipSetDevice");

@@ -1,82 +1,29 @@
-// dune-hdd_amd/csrc/kernels/rhs.hip -- right-hand sides and products of SWIPDG::init()
+// dune-hdd_amd/csrc/kernels/rhs.hip -- right-hand side of SWIPDG::init()
 //
 // SWIPDG right-hand side: the functionals SWIPDG::init() adds to its walk
 // (dune/hdd/linearelliptic/discretizations/swipdg.hh:251-347):
 //   L2Volume(f)                 b_i += int_K f phi_i
 //   DirichletBoundarySWIPDG     b_i += int_F -kappa g_D (A grad phi_i).n + sigma_b kappa (n.A n) / |F|^beta g_D phi_i
 //   L2Face(g_N) (Neumann faces) b_i += int_F g_N phi_i
-// for P1 triangles, Q1 quadrilaterals and Q_p hexahedra.  One thread per (owned element, basis function):
+// for P1 triangles, Q1 quadrilaterals and Q_p hexahedra.  rhs_kernel: one thread per (owned element, basis function):
 // the vector has nb entries per element (work O(nb nq) per element, negligible next to the matrix), so
-// the kernel is written for generality, not for a roofline.  Quadrature rules come from the host.
+// the kernel is written for generality, not for a roofline; its element helpers are elem_affine.hh's, shared with the
+// generic products (products.hip).  rhs2d_kernel / rhs2d_face_kernel: the P1 / Q1 hot path, one thread per element.
+// Quadrature rules come from the host.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdint>
+#include <type_traits>
 
-#include "swipdg_kernels.hh"
-#include "flattop.hh"
-#include "trig_phase.hh"
+#include "elem_affine.hh"
 
 namespace hdd {
 namespace dev {
 
-__device__ __forceinline__ double rhs_fn(const KappaArg& f, int64_t e, const double* x, int dim)
-{
-  switch (f.kind) {
-    case HDD_FN_PER_ELEM: return f.per_elem[e];
-    case HDD_FN_SINUSOID: return f.c + f.b * sin_phase(f.kx * x[0] + f.ky * x[1]);
-    case HDD_FN_FLATTOP: return flattop_sum(f.table, f.n_table, f.c, f.b, x[0], x[1]);
-    case HDD_FN_COS_PRODUCT:
-      return f.c * cos_phase(f.kx * x[0]) * cos_phase(f.ky * x[1]) * ((dim == 3 && f.b != 0.0) ? cos_phase(f.b * x[2]) : 1.0);
-    default: return f.c;
-  }
-}
-
-__device__ __forceinline__ void lagr(int p, int k, double x, double& v, double& d)
-{
-  double val = 1.0, der = 0.0;
-  for (int m = 0; m <= p; ++m) {
-    if (m == k) continue;
-    const double den = double(k - m) / p, f = (x - double(m) / p) / den;
-    der = der * f + val / den;
-    val *= f;
-  }
-  v = val;
-  d = der;
-}
-
-// basis function i and its reference gradient at the reference point xh
-__device__ void rhs_basis(int et, int p, int i, const double* xh, double& v, double* g)
-{
-  if (et == HDD_SIMPLEX) {
-    const double l[3] = {1.0 - xh[0] - xh[1], xh[0], xh[1]};
-    const double gx[3] = {-1.0, 1.0, 0.0}, gy[3] = {-1.0, 0.0, 1.0};
-    v = l[i];
-    g[0] = gx[i];
-    g[1] = gy[i];
-    return;
-  }
-  const int dim = et == HDD_HEX ? 3 : 2;
-  const int np = p + 1;
-  double lv[3], ld[3];
-  int r = i;
-  for (int a = 0; a < dim; ++a) {
-    lagr(p, r % np, xh[a], lv[a], ld[a]);
-    r /= np;
-  }
-  v = 1.0;
-  for (int a = 0; a < dim; ++a) v *= lv[a];
-  for (int b = 0; b < dim; ++b) {
-    double gb = 1.0;
-    for (int a = 0; a < dim; ++a) gb *= a == b ? ld[a] : lv[a];
-    g[b] = gb;
-  }
-}
-
 __global__ __launch_bounds__(256) void rhs_kernel(RhsArgs a)
 {
   const int dim = a.elem_type == HDD_HEX ? 3 : 2;
-  const int nvpe = a.elem_type == HDD_SIMPLEX ? 3 : (a.elem_type == HDD_CUBE ? 4 : 8);
   const int nf = a.elem_type == HDD_SIMPLEX ? 3 : (a.elem_type == HDD_CUBE ? 4 : 6);
   const int64_t n_own = a.own_end - a.own_begin;
   const int64_t total = n_own * a.nb;
@@ -85,42 +32,16 @@ __global__ __launch_bounds__(256) void rhs_kernel(RhsArgs a)
     const int i = int(t - k * a.nb);
     const int64_t e = a.own_begin + k;
     const int64_t n = a.n_local;
-    // affine geometry x = v0 + J xh (columns: vertices 1, 2 (, 4) minus vertex 0)
-    const int vcol[3] = {1, 2, 4};
-    double v0[3] = {0, 0, 0}, J[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int c = 0; c < dim; ++c) v0[c] = a.coords[c * n + e];
-    for (int j = 0; j < dim; ++j)
-      for (int c = 0; c < dim; ++c) J[c][j] = a.coords[(dim * vcol[j] + c) * n + e] - v0[c];
-    (void)nvpe;
-    double Ji[3][3], det;
-    if (dim == 2) {
-      det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-      Ji[0][0] = J[1][1] / det; Ji[0][1] = -J[0][1] / det;
-      Ji[1][0] = -J[1][0] / det; Ji[1][1] = J[0][0] / det;
-    } else {
-      const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-      const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-      const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-      det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-      Ji[0][0] = c00 / det; Ji[1][0] = c01 / det; Ji[2][0] = c02 / det;
-      Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / det;
-      Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / det;
-      Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / det;
-      Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / det;
-      Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / det;
-      Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / det;
-    }
+    double v0[3], J[3][3], Ji[3][3], det;
+    elem_geo(a.coords, n, e, dim, v0, J, Ji, det);
     double acc = 0.0;
     double xh[3] = {0, 0, 0}, x[3] = {0, 0, 0}, v, gh[3];
     if (a.has_force) {
       for (int q = 0; q < a.nqv; ++q) {
         for (int c = 0; c < dim; ++c) xh[c] = a.qv[q][c];
-        for (int c = 0; c < dim; ++c) {
-          x[c] = v0[c];
-          for (int j = 0; j < dim; ++j) x[c] += J[c][j] * xh[j];
-        }
-        rhs_basis(a.elem_type, a.degree, i, xh, v, gh);
-        acc += a.qv[q][3] * fabs(det) * rhs_fn(a.force, e, x, dim) * v;
+        elem_point(v0, J, dim, xh, x);
+        basis_value(a.elem_type, a.degree, i, xh, v, gh);
+        acc += a.qv[q][3] * fabs(det) * fn_value(a.force, e, x, dim) * v;
       }
     }
     if (a.has_dirichlet || a.has_neumann) {
@@ -129,61 +50,15 @@ __global__ __launch_bounds__(256) void rhs_kernel(RhsArgs a)
         const bool dir = nbr == HDD_NBR_DIRICHLET && a.has_dirichlet;
         const bool neu = nbr == HDD_NBR_NEUMANN && a.has_neumann;
         if (!dir && !neu) continue;
-        // reference face: corner r0 and spanning vectors t1 (, t2), reference outer normal nr
-        double r0[3] = {0, 0, 0}, t1[3] = {0, 0, 0}, t2[3] = {0, 0, 0}, nr[3] = {0, 0, 0};
-        if (a.elem_type == HDD_SIMPLEX) {
-          // faces (v0,v1), (v0,v2), (v1,v2) of the reference triangle (0,0), (1,0), (0,1)
-          const double P[3][2] = {{0, 0}, {1, 0}, {0, 1}};
-          const int fv[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-          const double N[3][2] = {{0, -1}, {-1, 0}, {1, 1}};
-          for (int c = 0; c < 2; ++c) {
-            r0[c] = P[fv[f][0]][c];
-            t1[c] = P[fv[f][1]][c] - P[fv[f][0]][c];
-            nr[c] = N[f][c];
-          }
-        } else {
-          const int af = f >> 1, sd = f & 1;
-          r0[af] = sd;
-          nr[af] = sd ? 1.0 : -1.0;
-          int b0 = -1, b1 = -1;
-          for (int c = 0; c < dim; ++c)
-            if (c != af) { if (b0 < 0) b0 = c; else b1 = c; }
-          t1[b0] = 1.0;
-          if (dim == 3) t2[b1] = 1.0;
-        }
-        // physical normal J^{-T} nr / |.| and face measure
-        double nv[3] = {0, 0, 0};
-        for (int c = 0; c < dim; ++c)
-          for (int j = 0; j < dim; ++j) nv[c] += Ji[j][c] * nr[j];
-        double nn = 0.0;
-        for (int c = 0; c < dim; ++c) nn += nv[c] * nv[c];
-        nn = sqrt(nn);
-        for (int c = 0; c < dim; ++c) nv[c] /= nn;
-        double fvol;
-        if (dim == 2) {
-          const double dx = J[0][0] * t1[0] + J[0][1] * t1[1], dy = J[1][0] * t1[0] + J[1][1] * t1[1];
-          fvol = sqrt(dx * dx + dy * dy);
-        } else {
-          fvol = fabs(det) * nn;   // reference face area 1 (Nanson)
-        }
+        double r0[3], t1[3], t2[3], nr[3], nv[3];
+        ref_face(a.elem_type, f, r0, t1, t2, nr);
+        const double fvol = face_normal(J, Ji, det, dim, t1, nr, nv);
         const double* qs = dir ? &a.qd[0][0] : &a.qn[0][0];
         const int nq = dir ? a.nqd : a.nqn;
         double An[3] = {0, 0, 0}, gamma = 0.0;
         if (dir) {
-          double A[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-          if (a.tkind == HDD_TENSOR_ISO_PER_ELEM) {
-            for (int c = 0; c < dim; ++c) A[c][c] = a.tper[e];
-          } else {
-            const int ns = dim == 2 ? 3 : 6;
-            double cc[6];
-            for (int r = 0; r < ns; ++r) cc[r] = a.tkind == HDD_TENSOR_SYM_PER_ELEM ? a.tper[r * n + e] : a.tc[r];
-            if (dim == 2) {
-              A[0][0] = cc[0]; A[0][1] = A[1][0] = cc[1]; A[1][1] = cc[2];
-            } else {
-              A[0][0] = cc[0]; A[0][1] = A[1][0] = cc[1]; A[0][2] = A[2][0] = cc[2];
-              A[1][1] = cc[3]; A[1][2] = A[2][1] = cc[4]; A[2][2] = cc[5];
-            }
-          }
+          double A[3][3];
+          elem_tensor(a.tkind, a.tc, a.tper, n, e, dim, A);
           for (int c = 0; c < dim; ++c)
             for (int j = 0; j < dim; ++j) An[c] += A[c][j] * nv[j];
           for (int c = 0; c < dim; ++c) gamma += nv[c] * An[c];
@@ -192,14 +67,11 @@ __global__ __launch_bounds__(256) void rhs_kernel(RhsArgs a)
         for (int q = 0; q < nq; ++q) {
           const double s0 = qs[3 * q], s1 = qs[3 * q + 1], w = qs[3 * q + 2];
           for (int c = 0; c < dim; ++c) xh[c] = r0[c] + s0 * t1[c] + s1 * t2[c];
-          for (int c = 0; c < dim; ++c) {
-            x[c] = v0[c];
-            for (int j = 0; j < dim; ++j) x[c] += J[c][j] * xh[j];
-          }
-          rhs_basis(a.elem_type, a.degree, i, xh, v, gh);
-          const double gv = w * fvol * rhs_fn(dir ? a.dirichlet : a.neumann, e, x, dim);
+          elem_point(v0, J, dim, xh, x);
+          basis_value(a.elem_type, a.degree, i, xh, v, gh);
+          const double gv = w * fvol * fn_value(dir ? a.dirichlet : a.neumann, e, x, dim);
           if (dir) {
-            const double kap = rhs_fn(a.kappa, e, x, dim);
+            const double kap = fn_value(a.kappa, e, x, dim);
             double gp = 0.0;   // (A grad phi_i) . n = (J^{-1} A n) . grad_ref phi_i
             for (int r = 0; r < dim; ++r) {
               double cr = 0.0;
@@ -234,7 +106,30 @@ __device__ __forceinline__ void rhs2d_shape(double x, double y, double* v, doubl
   }
 }
 
-// Dirichlet / Neumann faces of element e, added to acc in face order (the same rounding wherever it runs)
+// vertices 0, 1, 2 of an element (they span its affine map)
+struct Verts2 {
+  double x0, y0, x1, y1, x2, y2;
+};
+
+// VX: by the element's vertex ids from the 16-byte vertex rows; else element e of the element-major coordinates
+template <bool VX>
+__device__ __forceinline__ Verts2 rhs2d_vertices(const RhsArgs& a, int64_t e, int32_t vi0, int32_t vi1, int32_t vi2)
+{
+  if constexpr (VX) {
+    const double2 p0 = reinterpret_cast<const double2*>(a.vxy)[vi0];
+    const double2 p1 = reinterpret_cast<const double2*>(a.vxy)[vi1];
+    const double2 p2 = reinterpret_cast<const double2*>(a.vxy)[vi2];
+    return Verts2{p0.x, p0.y, p1.x, p1.y, p2.x, p2.y};
+  } else {
+    const int64_t n = a.n_local;
+    return Verts2{a.coords[e], a.coords[n + e], a.coords[2 * n + e], a.coords[3 * n + e], a.coords[4 * n + e],
+                  a.coords[5 * n + e]};
+  }
+}
+
+// Dirichlet / Neumann faces of element e, added to acc in face order (the same rounding wherever it runs).  The
+// reference face is elem_affine.hh's (constants once f is unrolled); the arithmetic is this path's own scalar 2d
+// form, not the generic 3 x 3 loops: its registers decide the face kernel's occupancy.
 template <bool TRI>
 __device__ __forceinline__ void rhs2d_faces(const RhsArgs& a, int64_t e, double x0, double y0, double j00, double j10,
                                             double j01, double j11, double det, double* acc)
@@ -249,22 +144,8 @@ __device__ __forceinline__ void rhs2d_faces(const RhsArgs& a, int64_t e, double 
     const bool dir = nbr == HDD_NBR_DIRICHLET && a.has_dirichlet;
     const bool neu = nbr == HDD_NBR_NEUMANN && a.has_neumann;
     if (!dir && !neu) continue;
-    double r0[2] = {0, 0}, t1[2] = {0, 0}, nr[2] = {0, 0};
-    if constexpr (TRI) {
-      const double P[3][2] = {{0, 0}, {1, 0}, {0, 1}};
-      const int fv[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-      const double N[3][2] = {{0, -1}, {-1, 0}, {1, 1}};
-      for (int c = 0; c < 2; ++c) {
-        r0[c] = P[fv[f][0]][c];
-        t1[c] = P[fv[f][1]][c] - P[fv[f][0]][c];
-        nr[c] = N[f][c];
-      }
-    } else {
-      const int af = f >> 1, sd = f & 1;
-      r0[af] = sd;
-      nr[af] = sd ? 1.0 : -1.0;
-      t1[1 - af] = 1.0;
-    }
+    double r0[3], t1[3], t2[3], nr[3];
+    ref_face(TRI ? HDD_SIMPLEX : HDD_CUBE, f, r0, t1, t2, nr);
     double nvx = i00 * nr[0] + i10 * nr[1], nvy = i01 * nr[0] + i11 * nr[1];
     const double nn = sqrt(nvx * nvx + nvy * nvy);
     nvx /= nn;
@@ -296,9 +177,9 @@ __device__ __forceinline__ void rhs2d_faces(const RhsArgs& a, int64_t e, double 
       xq[0] = x0 + j00 * xh + j01 * yh;
       xq[1] = y0 + j10 * xh + j11 * yh;
       rhs2d_shape<TRI>(xh, yh, v, gx, gy);
-      const double gv = w * fvol * rhs_fn(dir ? a.dirichlet : a.neumann, e, xq, 2);
+      const double gv = w * fvol * fn_value(dir ? a.dirichlet : a.neumann, e, xq, 2);
       if (dir) {
-        const double kap = rhs_fn(a.kappa, e, xq, 2);
+        const double kap = fn_value(a.kappa, e, xq, 2);
         const double pen = a.sigma_boundary * kap * gamma / hpow;
 #pragma unroll
         for (int i = 0; i < NB; ++i) acc[i] += gv * (-kap * (cr0 * gx[i] + cr1 * gy[i]) + pen * v[i]);
@@ -324,21 +205,14 @@ __global__ __launch_bounds__(256) void rhs2d_kernel(RhsArgs a)
   const int64_t n = a.n_local;
   for (int64_t k = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; k < n_own; k += int64_t(gridDim.x) * blockDim.x) {
     const int64_t e = a.own_begin + k;
-    double x0, y0, x1, y1, x2, y2;
-    [[maybe_unused]] int32_t vi0 = 0, vi1 = 0, vi2 = 0;
+    int32_t vi0 = 0, vi1 = 0, vi2 = 0;
     if constexpr (VX) {
       vi0 = a.ev[e]; vi1 = a.ev[n + e]; vi2 = a.ev[2 * n + e];
-      const double2 p0 = reinterpret_cast<const double2*>(a.vxy)[vi0];
-      const double2 p1 = reinterpret_cast<const double2*>(a.vxy)[vi1];
-      const double2 p2 = reinterpret_cast<const double2*>(a.vxy)[vi2];
-      x0 = p0.x; y0 = p0.y; x1 = p1.x; y1 = p1.y; x2 = p2.x; y2 = p2.y;
-    } else {
-      x0 = a.coords[e]; y0 = a.coords[n + e];
-      x1 = a.coords[2 * n + e]; y1 = a.coords[3 * n + e];
-      x2 = a.coords[4 * n + e]; y2 = a.coords[5 * n + e];
     }
-    const double j00 = x1 - x0, j10 = y1 - y0;   // vertex 1 - vertex 0
-    const double j01 = x2 - x0, j11 = y2 - y0;   // vertex 2 - vertex 0
+    const Verts2 p = rhs2d_vertices<VX>(a, e, vi0, vi1, vi2);
+    const double x0 = p.x0, y0 = p.y0;
+    const double j00 = p.x1 - x0, j10 = p.y1 - y0;   // vertex 1 - vertex 0
+    const double j01 = p.x2 - x0, j11 = p.y2 - y0;   // vertex 2 - vertex 0
     const double det = j00 * j11 - j01 * j10, adet = fabs(det);
     double acc[NB];
 #pragma unroll
@@ -374,7 +248,7 @@ __global__ __launch_bounds__(256) void rhs2d_kernel(RhsArgs a)
         else
           f = a.force.c * cos_phase(a.force.kx * xq[0]) * cos_phase(a.force.ky * xq[1]);
       }
-      else f = rhs_fn(a.force, e, xq, 2);
+      else f = fn_value(a.force, e, xq, 2);
       const double fv = a.qv[q][3] * adet * f;
 #pragma unroll
       for (int i = 0; i < NB; ++i) acc[i] += fv * v[i];
@@ -389,8 +263,9 @@ __global__ __launch_bounds__(256) void rhs2d_kernel(RhsArgs a)
     }
     if (a.has_dirichlet || a.has_neumann) {
       if constexpr (SPLIT) {
-        // boundary elements (~0.4 % at C2) go to rhs2d_face_kernel: the face code's registers (203 VGPRs
-        // fused, 2 waves per SIMD) stay out of this kernel (63 VGPRs, 7 waves per SIMD)
+        // boundary elements (~0.4 % at C2) go to rhs2d_face_kernel: the face code's registers (fused, unrolled rule:
+        // 205 VGPRs for P1, 256 for Q1, 2 waves per SIMD) stay out of this kernel (68-72 VGPRs and 7 waves per SIMD
+        // for P1, 134-138 and 3 for Q1; every instantiation: profiles/r13/rhs/kernel_resources.txt)
         bool bnd = false;
 #pragma unroll
         for (int f = 0; f < NF; ++f) {
@@ -425,7 +300,6 @@ template <bool TRI, bool VX>
 __global__ __launch_bounds__(256) void rhs2d_face_kernel(RhsArgs a)
 {
   constexpr int NB = TRI ? 3 : 4;
-  const int64_t n = a.n_local;
   const uint4* list = reinterpret_cast<const uint4*>(a.bnd_list + RHS_LIST_OFS);
   const uint32_t n_own = uint32_t(a.own_end - a.own_begin), stride = gridDim.x * blockDim.x;
   uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -434,23 +308,13 @@ __global__ __launch_bounds__(256) void rhs2d_face_kernel(RhsArgs a)
   for (; t < count; t += stride) {
     const int64_t k = ent.x;
     const int64_t e = a.own_begin + k;
-    double x0, y0, x1, y1, x2, y2;
-    if constexpr (VX) {
-      const double2 p0 = reinterpret_cast<const double2*>(a.vxy)[ent.y];
-      const double2 p1 = reinterpret_cast<const double2*>(a.vxy)[ent.z];
-      const double2 p2 = reinterpret_cast<const double2*>(a.vxy)[ent.w];
-      x0 = p0.x; y0 = p0.y; x1 = p1.x; y1 = p1.y; x2 = p2.x; y2 = p2.y;
-    } else {
-      x0 = a.coords[e]; y0 = a.coords[n + e];
-      x1 = a.coords[2 * n + e]; y1 = a.coords[3 * n + e];
-      x2 = a.coords[4 * n + e]; y2 = a.coords[5 * n + e];
-    }
-    const double j00 = x1 - x0, j10 = y1 - y0, j01 = x2 - x0, j11 = y2 - y0;
+    const Verts2 p = rhs2d_vertices<VX>(a, e, int32_t(ent.y), int32_t(ent.z), int32_t(ent.w));
+    const double j00 = p.x1 - p.x0, j10 = p.y1 - p.y0, j01 = p.x2 - p.x0, j11 = p.y2 - p.y0;
     const double det = j00 * j11 - j01 * j10;
     double acc[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) acc[i] = a.out[k * NB + i];
-    rhs2d_faces<TRI>(a, e, x0, y0, j00, j10, j01, j11, det, acc);
+    rhs2d_faces<TRI>(a, e, p.x0, p.y0, j00, j10, j01, j11, det, acc);
 #pragma unroll
     for (int i = 0; i < NB; ++i) a.out[k * NB + i] = acc[i];
     if (t + stride < count) ent = list[t + stride];
@@ -466,318 +330,51 @@ __global__ __launch_bounds__(256) void rhs2d_face_kernel(RhsArgs a)
   }
 }
 
-// ---------------------------------------------------------------------------------------------------
-// products of SWIPDG::init() (swipdg.hh:358-508, over_integrate = 2): one thread per matrix entry
-//   L2 phi_i phi_j, H1_SEMI grad.grad, ELLIPTIC kappa (A grad phi_j).grad phi_i, BOUNDARY_L2 on every
-//   boundary face -- element-local blocks (volume pattern, row length nb);
-//   PENALTY: sigma kappa^- kappa^+ gamma / |F|^beta [u][v] on inner faces and the boundary penalty on Dirichlet
-//   faces -- SWIPDG face pattern (owner-computes rows: self block and one block per inner face).
-// ---------------------------------------------------------------------------------------------------
-struct PGeo {
-  double v0[3], J[3][3], Ji[3][3], det;
-};
-
-__device__ void p_geo(const ProductArgs& a, int64_t e, int dim, PGeo& G)
+// f(bool_constant, ..) for run-time bools: one call site instantiates a kernel for every combination
+template <class F>
+static void with_bools(F&& f)
 {
-  const int vcol[3] = {1, 2, 4};
-  const int64_t n = a.n_local;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) { G.J[r][c] = r == c; G.Ji[r][c] = r == c; }
-  for (int c = 0; c < 3; ++c) G.v0[c] = 0.0;
-  for (int c = 0; c < dim; ++c) G.v0[c] = a.coords[c * n + e];
-  for (int j = 0; j < dim; ++j)
-    for (int c = 0; c < dim; ++c) G.J[c][j] = a.coords[(dim * vcol[j] + c) * n + e] - G.v0[c];
-  double(*J)[3] = G.J;
-  if (dim == 2) {
-    G.det = J[0][0] * J[1][1] - J[0][1] * J[1][0];
-    G.Ji[0][0] = J[1][1] / G.det; G.Ji[0][1] = -J[0][1] / G.det;
-    G.Ji[1][0] = -J[1][0] / G.det; G.Ji[1][1] = J[0][0] / G.det;
-  } else {
-    const double c00 = J[1][1] * J[2][2] - J[1][2] * J[2][1];
-    const double c01 = J[1][2] * J[2][0] - J[1][0] * J[2][2];
-    const double c02 = J[1][0] * J[2][1] - J[1][1] * J[2][0];
-    G.det = J[0][0] * c00 + J[0][1] * c01 + J[0][2] * c02;
-    G.Ji[0][0] = c00 / G.det; G.Ji[1][0] = c01 / G.det; G.Ji[2][0] = c02 / G.det;
-    G.Ji[0][1] = (J[0][2] * J[2][1] - J[0][1] * J[2][2]) / G.det;
-    G.Ji[1][1] = (J[0][0] * J[2][2] - J[0][2] * J[2][0]) / G.det;
-    G.Ji[2][1] = (J[0][1] * J[2][0] - J[0][0] * J[2][1]) / G.det;
-    G.Ji[0][2] = (J[0][1] * J[1][2] - J[0][2] * J[1][1]) / G.det;
-    G.Ji[1][2] = (J[0][2] * J[1][0] - J[0][0] * J[1][2]) / G.det;
-    G.Ji[2][2] = (J[0][0] * J[1][1] - J[0][1] * J[1][0]) / G.det;
-  }
+  f();
 }
-
-__device__ void p_tensor(const ProductArgs& a, int64_t e, int dim, double A[3][3])
+template <class F, class... Bools>
+static void with_bools(F&& f, bool b, Bools... rest)
 {
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) A[r][c] = 0.0;
-  if (a.tkind == HDD_TENSOR_ISO_PER_ELEM) {
-    for (int c = 0; c < dim; ++c) A[c][c] = a.tper[e];
-    return;
-  }
-  const int ns = dim == 2 ? 3 : 6;
-  double cc[6];
-  for (int r = 0; r < ns; ++r) cc[r] = a.tkind == HDD_TENSOR_SYM_PER_ELEM ? a.tper[r * a.n_local + e] : a.tc[r];
-  if (dim == 2) {
-    A[0][0] = cc[0]; A[0][1] = A[1][0] = cc[1]; A[1][1] = cc[2];
-  } else {
-    A[0][0] = cc[0]; A[0][1] = A[1][0] = cc[1]; A[0][2] = A[2][0] = cc[2];
-    A[1][1] = cc[3]; A[1][2] = A[2][1] = cc[4]; A[2][2] = cc[5];
-  }
-}
-
-// reference face: corner r0, spanning vectors t1, t2, reference outer normal nr
-__device__ void p_face(int et, int f, double* r0, double* t1, double* t2, double* nr)
-{
-  for (int c = 0; c < 3; ++c) { r0[c] = 0.0; t1[c] = 0.0; t2[c] = 0.0; nr[c] = 0.0; }
-  if (et == HDD_SIMPLEX) {
-    const double P[3][2] = {{0, 0}, {1, 0}, {0, 1}};
-    const int fv[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-    const double N[3][2] = {{0, -1}, {-1, 0}, {1, 1}};
-    for (int c = 0; c < 2; ++c) {
-      r0[c] = P[fv[f][0]][c];
-      t1[c] = P[fv[f][1]][c] - P[fv[f][0]][c];
-      nr[c] = N[f][c];
-    }
-    return;
-  }
-  const int dim = et == HDD_HEX ? 3 : 2;
-  const int af = f >> 1, sd = f & 1;
-  r0[af] = sd;
-  nr[af] = sd ? 1.0 : -1.0;
-  int b0 = -1, b1 = -1;
-  for (int c = 0; c < dim; ++c)
-    if (c != af) { if (b0 < 0) b0 = c; else b1 = c; }
-  t1[b0] = 1.0;
-  if (dim == 3) t2[b1] = 1.0;
-}
-
-__global__ __launch_bounds__(256) void product_kernel(ProductArgs a)
-{
-  const int et = a.elem_type, dim = et == HDD_HEX ? 3 : 2, nb = a.nb;
-  const int nf = et == HDD_SIMPLEX ? 3 : (et == HDD_CUBE ? 4 : 6);
-  const bool penalty = a.kind == HDD_PRODUCT_PENALTY;
-  const int64_t n_own = a.own_end - a.own_begin;
-  const int64_t n = a.n_local;
-  const int64_t width = penalty ? int64_t(nb) * 7 : nb;     // entries per row (upper bound for the penalty)
-  const int64_t total = n_own * nb * width;
-  for (int64_t t = blockIdx.x * int64_t(blockDim.x) + threadIdx.x; t < total; t += int64_t(gridDim.x) * blockDim.x) {
-    const int64_t k = t / (nb * width);
-    const int i = int((t / width) % nb);
-    const int64_t cidx = t % width;
-    const int64_t e = a.own_begin + k;
-    int32_t nbr[6];
-    int nblk = 1;
-    for (int f = 0; f < nf; ++f) {
-      nbr[f] = a.nbrs[f * n + e];
-      nblk += nbr[f] >= 0;
-    }
-    const int64_t rl = penalty ? int64_t(nb) * nblk : nb;
-    if (cidx >= rl) continue;
-    const int blk = int(cidx / nb), j = int(cidx % nb);
-    PGeo G;
-    p_geo(a, e, dim, G);
-    double acc = 0.0, xh[3] = {0, 0, 0}, x[3] = {0, 0, 0}, vi, vj, gi[3], gj[3];
-    if (a.kind <= HDD_PRODUCT_ELLIPTIC) {
-      double A[3][3];
-      if (a.kind == HDD_PRODUCT_ELLIPTIC) p_tensor(a, e, dim, A);
-      const int nq = et == HDD_SIMPLEX ? a.nqv : (dim == 2 ? a.nqv * a.nqv : a.nqv * a.nqv * a.nqv);
-      for (int q = 0; q < nq; ++q) {
-        double w;
-        if (et == HDD_SIMPLEX) {
-          xh[0] = a.qv[q][0]; xh[1] = a.qv[q][1]; w = a.qv[q][3];
-        } else {
-          int r = q;
-          w = 1.0;
-          for (int c = 0; c < dim; ++c) { xh[c] = a.qv[r % a.nqv][0]; w *= a.qv[r % a.nqv][3]; r /= a.nqv; }
-        }
-        rhs_basis(et, a.degree, i, xh, vi, gi);
-        rhs_basis(et, a.degree, j, xh, vj, gj);
-        double v;
-        if (a.kind == HDD_PRODUCT_L2) {
-          v = vi * vj;
-        } else {
-          double pi[3] = {0, 0, 0}, pj[3] = {0, 0, 0};   // physical gradients J^{-T} grad_ref
-          for (int c = 0; c < dim; ++c)
-            for (int r = 0; r < dim; ++r) { pi[c] += G.Ji[r][c] * gi[r]; pj[c] += G.Ji[r][c] * gj[r]; }
-          if (a.kind == HDD_PRODUCT_H1_SEMI) {
-            v = 0.0;
-            for (int c = 0; c < dim; ++c) v += pi[c] * pj[c];
-          } else {
-            for (int c = 0; c < dim; ++c) {
-              x[c] = G.v0[c];
-              for (int r = 0; r < dim; ++r) x[c] += G.J[c][r] * xh[r];
-            }
-            v = 0.0;
-            for (int c = 0; c < dim; ++c)
-              for (int r = 0; r < dim; ++r) v += A[c][r] * pj[r] * pi[c];
-            v *= rhs_fn(a.kappa, e, x, dim);
-          }
-        }
-        acc += w * fabs(G.det) * v;
-      }
-      a.vals[a.elem_ptr[k] + int64_t(i) * rl + cidx] = acc;
-      continue;
-    }
-    // face products: which element does column block `blk` belong to (blocks sorted by element id)
-    int64_t col_elem = -1;
-    {
-      int64_t ids[7];
-      int m = 0;
-      ids[m++] = e;
-      for (int f = 0; f < nf; ++f)
-        if (nbr[f] >= 0) ids[m++] = nbr[f];
-      for (int p = 1; p < m; ++p)
-        for (int q = p; q > 0 && ids[q - 1] > ids[q]; --q) { const int64_t tmp = ids[q]; ids[q] = ids[q - 1]; ids[q - 1] = tmp; }
-      col_elem = ids[blk];
-    }
-    const int nq1 = a.nq1f, nqf = dim == 2 ? nq1 : nq1 * nq1;
-    double A[3][3];
-    if (penalty) p_tensor(a, e, dim, A);
-    for (int f = 0; f < nf; ++f) {
-      const bool inner = nbr[f] >= 0;
-      if (a.kind == HDD_PRODUCT_BOUNDARY_L2 && inner) continue;
-      if (penalty) {
-        if (!inner && nbr[f] != HDD_NBR_DIRICHLET) continue;
-        if (col_elem != e && nbr[f] != col_elem) continue;   // neighbour block: only its face
-      }
-      double r0[3], t1[3], t2[3], nr[3];
-      p_face(et, f, r0, t1, t2, nr);
-      double nv[3] = {0, 0, 0}, nn = 0.0;
-      for (int c = 0; c < dim; ++c)
-        for (int r = 0; r < dim; ++r) nv[c] += G.Ji[r][c] * nr[r];
-      for (int c = 0; c < dim; ++c) nn += nv[c] * nv[c];
-      nn = sqrt(nn);
-      for (int c = 0; c < dim; ++c) nv[c] /= nn;
-      double fvol;
-      if (dim == 2) {
-        const double dx = G.J[0][0] * t1[0] + G.J[0][1] * t1[1], dy = G.J[1][0] * t1[0] + G.J[1][1] * t1[1];
-        fvol = sqrt(dx * dx + dy * dy);
-      } else {
-        fvol = fabs(G.det) * nn;
-      }
-      double pen_c = 1.0;   // sigma gamma / |F|^beta (without kappa)
-      PGeo Gn;
-      if (penalty) {
-        double An[3] = {0, 0, 0}, dm = 0.0;
-        for (int c = 0; c < dim; ++c)
-          for (int r = 0; r < dim; ++r) An[c] += A[c][r] * nv[r];
-        for (int c = 0; c < dim; ++c) dm += nv[c] * An[c];
-        double gam = dm, sig = a.sigma_boundary;
-        if (inner) {
-          double Ao[3][3], Ano[3] = {0, 0, 0}, dp = 0.0;
-          p_tensor(a, nbr[f], dim, Ao);
-          for (int c = 0; c < dim; ++c)
-            for (int r = 0; r < dim; ++r) Ano[c] += Ao[c][r] * nv[r];
-          for (int c = 0; c < dim; ++c) dp += nv[c] * Ano[c];
-          gam = dp * dm / (dp + dm);
-          sig = a.sigma_inner;
-          p_geo(a, nbr[f], dim, Gn);
-        }
-        pen_c = sig * gam / pow(fvol, a.beta);
-      }
-      for (int q = 0; q < nqf; ++q) {
-        const int qs = q % nq1, qt = q / nq1;
-        const double s0 = a.qf[qs][0], s1 = dim == 3 ? a.qf[qt][0] : 0.0;
-        const double w = a.qf[qs][1] * (dim == 3 ? a.qf[qt][1] : 1.0);
-        for (int c = 0; c < dim; ++c) xh[c] = r0[c] + s0 * t1[c] + s1 * t2[c];
-        rhs_basis(et, a.degree, i, xh, vi, gi);
-        if (!penalty) {
-          rhs_basis(et, a.degree, j, xh, vj, gj);
-          acc += w * fvol * vi * vj;
-          continue;
-        }
-        for (int c = 0; c < dim; ++c) {
-          x[c] = G.v0[c];
-          for (int r = 0; r < dim; ++r) x[c] += G.J[c][r] * xh[r];
-        }
-        const double ke = rhs_fn(a.kappa, e, x, dim);
-        const double fac = w * fvol * pen_c * ke * (inner ? rhs_fn(a.kappa, nbr[f], x, dim) : 1.0);
-        if (col_elem == e) {
-          rhs_basis(et, a.degree, j, xh, vj, gj);
-          acc += fac * vi * vj;
-        } else {
-          double xo[3] = {0, 0, 0};   // neighbour's reference coordinates of x
-          for (int r = 0; r < dim; ++r)
-            for (int c = 0; c < dim; ++c) xo[r] += Gn.Ji[r][c] * (x[c] - Gn.v0[c]);
-          rhs_basis(et, a.degree, j, xo, vj, gj);
-          acc -= fac * vi * vj;
-        }
-      }
-    }
-    a.vals[a.elem_ptr[k] + int64_t(i) * rl + cidx] = acc;
-  }
-}
-
-hipError_t launch_product(const ProductArgs& a, hipStream_t s)
-{
-  const int64_t width = a.kind == HDD_PRODUCT_PENALTY ? int64_t(a.nb) * 7 : a.nb;
-  const int64_t total = (a.own_end - a.own_begin) * a.nb * width;
-  if (total <= 0) return hipSuccess;
-  const int64_t blocks = (total + 255) / 256;
-  hipLaunchKernelGGL(product_kernel, dim3(unsigned(blocks < (1 << 20) ? blocks : (1 << 20))), dim3(256), 0, s, a);
-  return hipGetLastError();
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
 }
 
 hipError_t launch_rhs(const RhsArgs& a, hipStream_t s)
 {
   const int64_t n_own = a.own_end - a.own_begin;
   if (a.elem_type != HDD_HEX && n_own > 0) {
-    const int64_t blocks = std::min<int64_t>((n_own + 255) / 256, int64_t(a.n_cu) * 8);
-    const bool tri = a.elem_type == HDD_SIMPLEX;
-    // the ESV2007-type force (cos products) on the rules of order 4 (Dunavant 6 / Gauss 3 x 3): unrolled.
+    const bool tri = a.elem_type == HDD_SIMPLEX, vx = a.ev != nullptr;
+    // the ESV2007-type force (cos products) on the rules of order 4 (Dunavant 6 / Gauss 3 x 3): unrolled
+    const bool unrolled = a.has_force && a.force.kind == HDD_FN_COS_PRODUCT && a.nqv == (tri ? 6 : 9) && !a.generic;
     // split: volume kernel + boundary-element list + face kernel (needs the context's list, see RhsArgs)
-    if (a.bnd_list && (a.has_dirichlet || a.has_neumann)) {
-      const dim3 g(static_cast<unsigned>(blocks)), b(256);
-      if (a.has_force && a.force.kind == HDD_FN_COS_PRODUCT && a.nqv == (tri ? 6 : 9) && !a.generic) {
-        if (tri && a.ev) hipLaunchKernelGGL((rhs2d_kernel<true, true, 6, HDD_FN_COS_PRODUCT, true>), g, b, 0, s, a);
-        else if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, false, 6, HDD_FN_COS_PRODUCT, true>), g, b, 0, s, a);
-        else if (a.ev) hipLaunchKernelGGL((rhs2d_kernel<false, true, 9, HDD_FN_COS_PRODUCT, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((rhs2d_kernel<false, false, 9, HDD_FN_COS_PRODUCT, true>), g, b, 0, s, a);
-      } else if (a.ev) {
-        if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, true, 0, -1, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((rhs2d_kernel<false, true, 0, -1, true>), g, b, 0, s, a);
-      } else {
-        if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, false, 0, -1, true>), g, b, 0, s, a);
-        else hipLaunchKernelGGL((rhs2d_kernel<false, false, 0, -1, true>), g, b, 0, s, a);
-      }
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-      // a quarter of the CUs (16 K threads: one list entry per thread at C2's 7,680 boundary elements); every
-      // workgroup, busy or not, pays the finish atomic
-      const dim3 gf(unsigned(std::max(1, a.n_cu / 4)));
-      if (a.skip_face) {
-        e = hipErrorLaunchFailure;   // error injection (tests): the face launch did not happen
-      } else {
-        if (a.ev) {
-          if (tri) hipLaunchKernelGGL((rhs2d_face_kernel<true, true>), gf, b, 0, s, a);
-          else hipLaunchKernelGGL((rhs2d_face_kernel<false, true>), gf, b, 0, s, a);
-        } else {
-          if (tri) hipLaunchKernelGGL((rhs2d_face_kernel<true, false>), gf, b, 0, s, a);
-          else hipLaunchKernelGGL((rhs2d_face_kernel<false, false>), gf, b, 0, s, a);
-        }
-        e = hipGetLastError();
-      }
-      // the volume kernel has filled the list but no face kernel will reset it: re-arm the counters here, so the
-      // next call starts from an empty list (stream-ordered behind the volume kernel)
-      if (e != hipSuccess) (void)hipMemsetAsync(a.bnd_list, 0, 2 * sizeof(uint32_t), s);
-      return e;
-    }
-    if (a.has_force && a.force.kind == HDD_FN_COS_PRODUCT && a.nqv == (tri ? 6 : 9) && !a.generic) {
-      if (tri && a.ev) hipLaunchKernelGGL((rhs2d_kernel<true, true, 6, HDD_FN_COS_PRODUCT>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      else if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, false, 6, HDD_FN_COS_PRODUCT>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      else if (a.ev) hipLaunchKernelGGL((rhs2d_kernel<false, true, 9, HDD_FN_COS_PRODUCT>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((rhs2d_kernel<false, false, 9, HDD_FN_COS_PRODUCT>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      return hipGetLastError();
-    }
-    if (a.ev) {
-      if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, true>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((rhs2d_kernel<false, true>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
+    const bool split = a.bnd_list && (a.has_dirichlet || a.has_neumann);
+    const dim3 g(unsigned(std::min<int64_t>((n_own + 255) / 256, int64_t(a.n_cu) * 8))), b(256);
+    with_bools([&](auto tri_c, auto vx_c, auto unrolled_c, auto split_c) {
+      constexpr bool TRI = decltype(tri_c)::value, UNROLLED = decltype(unrolled_c)::value;
+      constexpr int NQ = UNROLLED ? (TRI ? 6 : 9) : 0, FK = UNROLLED ? int(HDD_FN_COS_PRODUCT) : -1;
+      hipLaunchKernelGGL((rhs2d_kernel<TRI, decltype(vx_c)::value, NQ, FK, decltype(split_c)::value>), g, b, 0, s, a);
+    }, tri, vx, unrolled, split);
+    hipError_t e = hipGetLastError();
+    if (!split || e != hipSuccess) return e;
+    // a quarter of the CUs (16 K threads: one list entry per thread at C2's 7,680 boundary elements); every
+    // workgroup, busy or not, pays the finish atomic
+    const dim3 gf(unsigned(std::max(1, a.n_cu / 4)));
+    if (a.skip_face) {
+      e = hipErrorLaunchFailure;   // error injection (tests): the face launch did not happen
     } else {
-      if (tri) hipLaunchKernelGGL((rhs2d_kernel<true, false>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((rhs2d_kernel<false, false>), dim3(unsigned(blocks)), dim3(256), 0, s, a);
+      with_bools([&](auto tri_c, auto vx_c) {
+        hipLaunchKernelGGL((rhs2d_face_kernel<decltype(tri_c)::value, decltype(vx_c)::value>), gf, b, 0, s, a);
+      }, tri, vx);
+      e = hipGetLastError();
     }
-    return hipGetLastError();
+    // the volume kernel has filled the list but no face kernel will reset it: re-arm the counters here, so the
+    // next call starts from an empty list (stream-ordered behind the volume kernel)
+    if (e != hipSuccess) (void)hipMemsetAsync(a.bnd_list, 0, 2 * sizeof(uint32_t), s);
+    return e;
   }
   const int64_t total = n_own * a.nb;
   if (total <= 0) return hipSuccess;

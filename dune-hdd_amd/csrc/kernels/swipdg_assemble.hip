@@ -39,7 +39,7 @@ static hipError_t launch_components(const AssembleArgs& a, int nqv, int nqf, hip
 
 // ------------------------------------------------------------------------------------------------
 // products (hdd_product_assemble) on the persistent driver: P1 / Q1 with piecewise-constant kappa; the
-// caller falls back to the generic product kernel (rhs.hip) for smooth kappa and hexahedra
+// caller falls back to the generic product kernel (products.hip) for smooth kappa and hexahedra
 // ------------------------------------------------------------------------------------------------
 hipError_t launch_product_fast(const AssembleArgs& a, int product, hipStream_t s, bool* supported)
 {

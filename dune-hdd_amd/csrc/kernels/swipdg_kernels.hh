@@ -170,7 +170,7 @@ constexpr int RHS_LIST_OFS = 64;
 inline size_t rhs_list_bytes(int64_t n_own) { return size_t(RHS_LIST_OFS) * sizeof(uint32_t) + size_t(n_own) * 16; }
 hipError_t launch_rhs(const RhsArgs& a, hipStream_t s);
 
-// products (rhs.hip): l2, h1_semi, elliptic, boundary_l2 (element-local blocks) and the SWIPDG penalty
+// products (products.hip): l2, h1_semi, elliptic, boundary_l2 (element-local blocks) and the SWIPDG penalty
 struct ProductArgs {
   int32_t elem_type, degree, nb, kind;
   int64_t n_local, own_begin, own_end;

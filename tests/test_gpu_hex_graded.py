@@ -1,4 +1,4 @@
-"""GPU parity of the Q_p hexahedral kernels (hex_qp.hip, rhs.hip) on a graded rectilinear mesh, where face
+"""GPU parity of the Q_p hexahedral kernels (hex_qp.hip, rhs.hip, products.hip) on a graded rectilinear mesh, where face
 neighbours differ in size, against the graded Q_p oracle (QpGrid(nodes=...), anchored by tests/test_oracle_qp.py).
 
 Every other hexahedral test runs on an equidistant box, on which the neighbour's Jacobian, |F| and h equal the

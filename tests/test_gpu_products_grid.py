@@ -3,7 +3,7 @@
 tile     the closed forms on the persistent tile driver (VolProductPolicy; the PEN instantiations of P1PwcPolicy and
          Q1PwcPolicy): the default DeviceMesh with piecewise-constant data.  hdd_last_tile_kernel() must name the
          expected policy with the expected tensor and kappa kind numbers, which proves that each instantiation ran.
-generic  product_kernel of rhs.hip: a mesh without face_info (piecewise-constant data) or a sinusoid kappa.  The
+generic  product_kernel of products.hip: a mesh without face_info (piecewise-constant data) or a sinusoid kappa.  The
          tile-kernel name must be the one a sentinel stiffness assembly left before the calls.
 
 Both are compared with the oracle, never with each other: row-wise (compare_rows, 1e-12, no floor, every row), the

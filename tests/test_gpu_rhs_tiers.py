@@ -10,7 +10,7 @@ meshes on which the Jacobian's off-diagonal entries enter the offsets of Q1 elem
 
 Every case runs (a) the force alone and (b) the force with Dirichlet data (sinusoid g_D, per-element kappa and
 iso tensor) on the unmarked and Neumann data on the marked boundary elements, on six contexts: the default, NO_TINY,
-GENERIC (run-time rule, rhs_fn's switch), FUSED, ELEMENT_MAJOR and FUSED | GENERIC."""
+GENERIC (run-time rule, fn_value's switch), FUSED, ELEMENT_MAJOR and FUSED | GENERIC."""
 import numpy as np
 import pytest
 
