@@ -141,6 +141,82 @@ int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const
   return HDD_OK;
 }
 
+int hdd::abi::plan_blocks(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                          int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds, ApplyPlan& P)
+{
+  if (!ctx || !pattern || !d_vals) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_blocks < 1 || n_blocks > HDD_MAX_SOLVE_BLOCKS) return fail(HDD_ERR_INVALID, who, "n_blocks outside 1..HDD_MAX_SOLVE_BLOCKS");
+  if (!bounds) return fail(HDD_ERR_INVALID, who, "null bounds");
+  for (int s = 0; s < n_blocks; ++s)
+    if (bounds[s] >= bounds[s + 1]) return fail(HDD_ERR_INVALID, who, "bounds not strictly ascending");
+  if (bounds[0] < 0 || bounds[n_blocks] > std::min(pattern->n_rows, pattern->n_cols))
+    return fail(HDD_ERR_INVALID, who, "bounds outside the square part of the matrix");
+  const hdd_block_range rg{bounds[0], bounds[n_blocks], bounds[0], bounds[n_blocks]};
+  if (int rc = plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, theta, &rg, P)) return rc;
+  bool aligned = true;
+  for (int s = 1; P.tile && s < n_blocks; ++s) aligned = aligned && bounds[s] % P.nb == 0;
+  // a segment that begins inside an element: what the single call on its range does
+  return aligned ? HDD_OK : plan_apply(who, ctx, nullptr, pattern, d_vals, n_comp, theta, &rg, P);
+}
+
+void hdd::abi::blocks_table(const hdd_ctx* ctx, const ApplyPlan& P, int32_t n_blocks, const int64_t* bounds, int block_size,
+                            int64_t max_parts, dev::BlockSegment* tab, int64_t (&total)[dev::BLOCKS_KINDS])
+{
+  for (int64_t& t : total) t = 0;
+  for (int s = 0; s < n_blocks; ++s) {
+    dev::BlockSegment& g = tab[s];
+    ApplyPlan Q = P;   // the plan of a call on this segment's range
+    dev::ApplyArgs& a = Q.a;
+    a.row_begin = a.col_begin = bounds[s];
+    a.row_end = a.col_end = bounds[s + 1];
+    if (P.tile) {
+      a.e_begin = a.own_begin + bounds[s] / P.nb;
+      a.e_end = a.own_begin + bounds[s + 1] / P.nb;
+      a.ce_begin = bounds[s] / P.nb;
+      a.ce_end = bounds[s + 1] / P.nb;
+    }
+    const int64_t rows = Q.rows();
+    g.row_begin = a.row_begin;
+    g.rows = rows;
+    g.e_begin = a.e_begin;
+    g.e_end = a.e_end;
+    int64_t grid[dev::BLOCKS_KINDS];
+    grid[dev::BLOCKS_DOT] = dot_grid(ctx, Q, max_parts);
+    grid[dev::BLOCKS_PARTS] = block_size ? std::max<int64_t>(1, std::min<int64_t>((rows / block_size + 255) / 256, 2048)) : 1;
+    grid[dev::BLOCKS_DIRECTION] = block_size ? std::max<int64_t>(1, std::min<int64_t>((rows + 255) / 256, 4096)) : 1;
+    grid[dev::BLOCKS_APPLY] = apply_grid(ctx, Q);
+    for (int k = 0; k < dev::BLOCKS_KINDS; ++k) {
+      g.first[k] = int32_t(total[k]);
+      g.grid[k] = int32_t(grid[k]);
+      total[k] += grid[k];
+    }
+  }
+}
+
+void hdd::abi::apply_blocks_kernel_name(std::string& out, const ApplyPlan& P, bool dot)
+{
+  out += P.tile ? "apply_tile_blocks_kernel<" : "apply_csr_blocks_kernel<";
+  out += P.tile ? (P.nb == 3 ? "3, 3" : "4, 4") : (P.short_rows ? "8" : "64");
+  out += dot ? ", dot>" : ">";
+}
+
+int hdd::abi::run_apply_blocks(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const dev::BlockSegment* d_tab, int32_t n_blocks,
+                               int64_t grid, const double* d_x, double* d_y, void* stream)
+{
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, who);
+  dev::ApplyArgs a = P.a;
+  a.nv = 1;
+  a.x = d_x;
+  a.y = d_y;
+  a.ldx = a.ldy = P.rows();
+  const dev::BlocksArgs B{d_tab, n_blocks, dev::BLOCKS_APPLY, P.a.row_begin, nullptr, nullptr};
+  last_apply_kernel_slot().clear();
+  apply_blocks_kernel_name(last_apply_kernel_slot(), P, false);
+  e = launch_apply_blocks<false>(P, a, B, grid, static_cast<hipStream_t>(stream));
+  return e == hipSuccess ? HDD_OK : hip_fail(e, who);
+}
+
 extern "C" const char* hdd_last_apply_kernel(void) { return last_apply_kernel_slot().c_str(); }
 
 namespace {
@@ -174,6 +250,31 @@ extern "C" int hdd_operator_apply(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_
                                   int64_t ldy, int32_t n_vec, void* stream)
 {
   return apply("hdd_operator_apply", false, ctx, mesh, pattern, d_vals, n_comp, theta, 0, range, d_x, ldx, d_y, ldy, n_vec, stream);
+}
+
+// The table goes through the context's pinned buffer into its device buffer (both as old as the context): the event
+// says when the previous call's copy has read the pinned one.
+extern "C" int hdd_operator_apply_blocks(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                                         int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds,
+                                         const double* d_x, double* d_y, void* stream)
+{
+  const char* who = "hdd_operator_apply_blocks";
+  if (!d_x || !d_y) return fail(HDD_ERR_INVALID, who, "null argument");
+  ApplyPlan P;
+  if (int rc = hdd::abi::plan_blocks(who, ctx, mesh, pattern, d_vals, n_comp, theta, n_blocks, bounds, P)) return rc;
+  if (!ctx->blocks_tab_h || !ctx->blocks_tab_d || !ctx->blocks_evt) return fail(HDD_ERR_INVALID, who, "context without its segment table");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipEventSynchronize(ctx->blocks_evt);
+  if (e != hipSuccess) return hip_fail(e, who);
+  auto* tab = static_cast<dev::BlockSegment*>(ctx->blocks_tab_h);
+  int64_t total[dev::BLOCKS_KINDS];
+  hdd::abi::blocks_table(ctx, P, n_blocks, bounds, 0, dev::APPLY2_BLOCKS, tab, total);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  e = hipMemcpyAsync(ctx->blocks_tab_d, tab, size_t(n_blocks) * sizeof(dev::BlockSegment), hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipEventRecord(ctx->blocks_evt, s);
+  if (e != hipSuccess) return hip_fail(e, who);
+  return hdd::abi::run_apply_blocks(who, ctx, P, static_cast<const dev::BlockSegment*>(ctx->blocks_tab_d), n_blocks,
+                                    total[dev::BLOCKS_APPLY], d_x, d_y, stream);
 }
 
 extern "C" int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern,

@@ -40,11 +40,21 @@ extern "C" int hdd_ctx_create(int hip_device, hdd_ctx** out)
     return hip_fail(e, "hdd_ctx_create: hipMalloc");
   }
   // hdd_operator_solve / _solve_batched read their states back at every look and may not allocate either
-  e = hipHostMalloc(reinterpret_cast<void**>(&c->solve_state_h), hdd_ctx::SOLVE_STATE_BYTES, hipHostMallocDefault);
+  static_assert(hdd_ctx::SOLVE_BLOCKS_BYTES >= hdd_ctx::SOLVE_STATE_BYTES, "one buffer for both");
+  e = hipHostMalloc(reinterpret_cast<void**>(&c->solve_state_h), hdd_ctx::SOLVE_BLOCKS_BYTES, hipHostMallocDefault);
   if (e != hipSuccess) {
     c->solve_state_h = nullptr;
     delete c;
     return hip_fail(e, "hdd_ctx_create: hipHostMalloc");
+  }
+  // the segment table of hdd_operator_apply_blocks / _solve_blocks
+  e = hipHostMalloc(&c->blocks_tab_h, hdd_ctx::SOLVE_BLOCKS_BYTES, hipHostMallocDefault);
+  if (e != hipSuccess) c->blocks_tab_h = nullptr;
+  if (e == hipSuccess && (e = hipMalloc(&c->blocks_tab_d, hdd_ctx::SOLVE_BLOCKS_BYTES)) != hipSuccess) c->blocks_tab_d = nullptr;
+  if (e == hipSuccess && (e = hipEventCreateWithFlags(&c->blocks_evt, hipEventDisableTiming)) != hipSuccess) c->blocks_evt = nullptr;
+  if (e != hipSuccess) {
+    delete c;
+    return hip_fail(e, "hdd_ctx_create: the segment table");
   }
   *out = c;
   return HDD_OK;

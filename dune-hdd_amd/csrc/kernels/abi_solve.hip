@@ -5,6 +5,8 @@
 // operator arguments are checked and dispatched by plan_apply (apply_plan.hh), as hdd_operator_apply's.
 // hdd_operator_solve_multi is the batched solve with a theta per column: the multi-theta applies and every column's
 // own inverse blocks.
+// hdd_operator_solve_blocks is the iteration on every segment of a partition of a row interval at once (the end of
+// this file): the same checks, its own workspace, setup and looks.
 // One driver serves the entries: checked (every argument check), Solve (the workspace and its two views), setup,
 // iterate (enqueue and look) and finish; an entry adds its own init-state kernel and its launches of one iteration.
 #include <hip/hip_runtime.h>
@@ -38,6 +40,8 @@ struct Entry {
 constexpr Entry SINGLE{"hdd_operator_solve", "hdd_operator_solve_workspace", int64_t(sizeof(dev::SolveState) / 8), true, false};
 // states of HDD_MAX_VEC columns, then the group words
 constexpr Entry BATCHED{"hdd_operator_solve_batched", "hdd_operator_solve_batched_workspace", int64_t(hdd_ctx::SOLVE_STATE_BYTES / 8), false, false};
+// (the segments' states, the stop word and the table: Solve::carve_blocks)
+constexpr Entry BLOCKS{"hdd_operator_solve_blocks", "hdd_operator_solve_blocks_workspace", 0, false, false};
 constexpr Entry MULTI{"hdd_operator_solve_multi", "hdd_operator_solve_multi_workspace", int64_t(hdd_ctx::SOLVE_STATE_BYTES / 8), false, true};
 
 std::string& last_solve_kernels_slot()
@@ -76,6 +80,17 @@ int64_t workspace_any(int64_t rows, int block_size, int n_rhs, const Entry& E)
   return w;
 }
 
+// hdd_operator_solve_blocks: per segment a state and a table entry (eight doubles each), the stop word's eight, the
+// partial sums of p . q (one per workgroup of the DOT apply: at most rows / 4 + 1 per segment, the CSR kernel with a
+// wave per row) and four kinds of one per workgroup of the update (at most rows / (256 bs) + 1 per segment), p q r z
+// and the inverse blocks of the interval
+int64_t blocks_pq(int64_t rows, int n_blocks) { return even(rows / 4 + n_blocks); }
+int64_t blocks_parts(int64_t rows, int bs, int n_blocks) { return even(rows / (256 * int64_t(bs)) + n_blocks); }
+int64_t blocks_workspace_doubles(int64_t rows, int bs, int n_blocks)
+{
+  return 16 * int64_t(n_blocks) + 8 + blocks_pq(rows, n_blocks) + 4 * blocks_parts(rows, bs, n_blocks) + 4 * even(rows) + blocks_doubles(rows, bs);
+}
+
 dim3 grid(int64_t g) { return dim3(unsigned(g)); }
 
 // a checked call: the plan, what the options resolve to, and the workspace
@@ -95,6 +110,30 @@ struct Solve {
   // at dinv + c * ld_dinv, its partial counts of indefinite blocks at part_pq + c * bad_stride; else zeros
   hdd::abi::ApplyThetas thetas;
   int64_t ld_dinv, bad_stride;
+  // hdd_operator_solve_blocks: the segments (n_seg == 0: another entry), the table in the workspace, the partial
+  // counts of indefinite blocks and the real workgroups per kind of launch
+  int n_seg = 0;
+  const int64_t* bounds;
+  dev::BlockSegment* tab;
+  double* part_bad;
+  int64_t total[dev::BLOCKS_KINDS];
+
+  void carve_blocks(double* w)
+  {
+    state = reinterpret_cast<dev::SolveState*>(w), w += 8 * int64_t(n_seg);
+    stop = reinterpret_cast<int32_t*>(w), w += 8;
+    tab = reinterpret_cast<dev::BlockSegment*>(w), w += 8 * int64_t(n_seg);
+    part_pq = w, w += blocks_pq(rows, n_seg);
+    for (double** part : {&part_rz, &part_rr, &part_bb, &part_bad}) *part = w, w += blocks_parts(rows, bs, n_seg);
+    for (double** vec : {&p, &q, &r, &z}) *vec = w, w += ldw;
+    if (!pre) z = r;
+    dinv = w;
+  }
+  dev::BlocksArgs blocks_args(int kind) const { return dev::BlocksArgs{tab, n_seg, kind, P.a.row_begin, stop, &state->done_at}; }
+  dev::SolveBlocks blocks() const
+  {
+    return dev::SolveBlocks{blocks_args(dev::BLOCKS_PARTS), state, stop, x, p, q, r, z, dinv, part_pq, part_rz, part_rr, part_bb, part_bad, history, ldh};
+  }
 
   void carve(double* w, int64_t head)
   {
@@ -128,12 +167,17 @@ struct Solve {
 int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals, int32_t n_comp,
             const double* theta, int64_t ldt, const hdd_block_range* range, const double* d_b, int64_t ldb, double* d_x, int64_t ldx, int32_t n_rhs,
             const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info,
-            void* stream, Solve& S)
+            void* stream, Solve& S, int32_t n_blocks = 0, const int64_t* bounds = nullptr)
 {
   const char* who = E.who;
+  const bool blocks = &E == &BLOCKS;   // one column over the interval (bounds[0], bounds[n_blocks]), an info per segment
   if (!d_b || !d_x || !opt || !d_work || !info) return fail(HDD_ERR_INVALID, who, "null argument");
   if (n_rhs < 1 || n_rhs > HDD_MAX_VEC) return fail(HDD_ERR_INVALID, who, "n_rhs outside 1..HDD_MAX_VEC");
-  if (int rc = hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, E.own ? nullptr : theta, range, S.P, E.own)) return rc;
+  if (blocks) {
+    if (int rc = hdd::abi::plan_blocks(who, ctx, mesh, pattern, d_vals, n_comp, theta, n_blocks, bounds, S.P)) return rc;
+    ldb = ldx = S.P.rows();
+  } else if (int rc = hdd::abi::plan_apply(who, ctx, mesh, pattern, d_vals, n_comp, E.own ? nullptr : theta, range, S.P, E.own))
+    return rc;
   if (E.own && theta && ldt < n_comp) return fail(HDD_ERR_INVALID, who, "ldt smaller than n_comp");
   const dev::ApplyArgs& a = S.P.a;
   if (a.row_begin != a.col_begin || a.row_end != a.col_end)
@@ -155,10 +199,12 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   const int64_t rows = a.row_end - a.row_begin;
   if (a.row_begin % bs != 0 || rows % bs != 0)
     return fail(HDD_ERR_INVALID, who, "the bounds of the range are not multiples of block_size");
+  for (int s = 1; s < n_blocks; ++s)
+    if (bounds[s] % bs != 0) return fail(HDD_ERR_INVALID, who, "the bounds of the segments are not multiples of block_size");
   if (E.dense) ldb = ldx = rows, ldh = int64_t(opt->max_iter) + 1;
   if (ldb < rows || ldx < rows) return fail(HDD_ERR_INVALID, who, "ldb / ldx smaller than the range");
   if (d_history && ldh < int64_t(opt->max_iter) + 1) return fail(HDD_ERR_INVALID, who, "ldh smaller than max_iter + 1");
-  if (n_work < workspace_doubles(rows, bs, n_rhs, E))
+  if (n_work < (blocks ? blocks_workspace_doubles(rows, bs, n_blocks) : workspace_doubles(rows, bs, n_rhs, E)))
     return fail(HDD_ERR_INVALID, who, (std::string("n_work smaller than ") + E.workspace).c_str());
   S.bs = bs;
   S.n_rhs = n_rhs;
@@ -168,7 +214,7 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
     return fail(HDD_ERR_INVALID, who, "pattern without row_ptr / col (block_size != nb of the mesh)");
   if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
   // ---- every argument check is above ----
-  for (int c = 0; c < n_rhs; ++c) info[c] = hdd_solve_info{HDD_SOLVE_CONVERGED, 0, 0.0, 0.0};
+  for (int c = 0; c < (blocks ? n_blocks : n_rhs); ++c) info[c] = hdd_solve_info{HDD_SOLVE_CONVERGED, 0, 0.0, 0.0};
   last_solve_kernels_slot().clear();
   S.x0 = (opt->flags & HDD_SOLVE_X0) != 0;
   S.rows = rows, S.ldb = ldb, S.ldx = ldx, S.ldw = even(rows), S.ldh = ldh;
@@ -183,7 +229,12 @@ int checked(const Entry& E, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* p
   S.bad_stride = E.own ? dev::SOLVE_PARTS : 0;
   // the 16-byte paths need every column of x aligned
   S.a16 = reinterpret_cast<uintptr_t>(d_work) % 16 == 0 && reinterpret_cast<uintptr_t>(d_x) % 16 == 0 && (n_rhs == 1 || ldx % 2 == 0);
-  S.carve(d_work, E.head);
+  if (blocks) {
+    S.n_seg = n_blocks;
+    S.bounds = bounds;
+    S.carve_blocks(d_work);
+  } else
+    S.carve(d_work, E.head);
   return HDD_OK;
 }
 
@@ -434,4 +485,118 @@ extern "C" int hdd_operator_solve_multi(hdd_ctx* ctx, const hdd_mesh* mesh, cons
 {
   return solve_columns(MULTI, ctx, mesh, pattern, d_vals, n_comp, theta, ldt, range, d_b, ldb, d_x, ldx, n_rhs, opt, d_work, n_work,
                        d_history, ldh, info, stream);
+}
+
+// ---- every segment of a partition per call -------------------------------------------------------------------------
+// The single solve's setup and iteration on the segments' virtual grids (solve_kernels.hh): the table goes from the
+// context's pinned buffer into the workspace in one copy, the inverse blocks of the whole interval are one launch,
+// an iteration is three launches whatever n_blocks is.  A look of the host is the stop-word launch and 64 bytes; the
+// states of all segments are read once, at the end.
+extern "C" int64_t hdd_operator_solve_blocks_workspace(int64_t rows, int32_t block_size, int32_t n_blocks)
+{
+  if (rows < 0 || block_size < 0 || block_size > 8 || n_blocks < 1 || n_blocks > HDD_MAX_SOLVE_BLOCKS) return 0;
+  int64_t w = 0;
+  for (int bs = block_size ? block_size : 1; bs <= (block_size ? block_size : 8); ++bs) w = std::max(w, blocks_workspace_doubles(rows, bs, n_blocks));
+  return w;
+}
+
+extern "C" int hdd_operator_solve_blocks(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                                         int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds,
+                                         const double* d_b, double* d_x, const hdd_solve_options* opt, double* d_work,
+                                         int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info, void* stream)
+{
+  const Entry& E = BLOCKS;
+  Solve S;
+  if (int rc = checked(E, ctx, mesh, pattern, d_vals, n_comp, theta, 0, nullptr, d_b, 0, d_x, 0, 1, opt, d_work, n_work, d_history, ldh, info,
+                       stream, S, n_blocks, bounds))
+    return rc;
+  if (!ctx->blocks_tab_h || !ctx->blocks_evt) return fail(HDD_ERR_INVALID, E.who, "context without its segment table");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e == hipSuccess) e = hipEventSynchronize(ctx->blocks_evt);   // an earlier upload has read the pinned table
+  if (e != hipSuccess) return hip_fail(e, E.who);
+  auto* tab = static_cast<dev::BlockSegment*>(ctx->blocks_tab_h);
+  hdd::abi::blocks_table(ctx, S.P, n_blocks, bounds, S.bs, dev::SOLVE_PARTS, tab, S.total);
+  if (S.total[dev::BLOCKS_DOT] > blocks_pq(S.rows, n_blocks) || S.total[dev::BLOCKS_PARTS] > blocks_parts(S.rows, S.bs, n_blocks))
+    return fail(HDD_ERR_INVALID, E.who, "more partial sums than the workspace holds");
+  e = hipMemcpyAsync(S.tab, tab, size_t(n_blocks) * sizeof(dev::BlockSegment), hipMemcpyHostToDevice, S.s);
+  if (e == hipSuccess) e = hipEventRecord(ctx->blocks_evt, S.s);
+  if (e != hipSuccess) return hip_fail(e, E.who);
+  std::string& nm = last_solve_kernels_slot();
+  hdd::abi::apply_blocks_kernel_name(nm, S.P, true);
+  nm += " + cg_update_blocks<" + std::to_string(S.bs) + (S.pre ? "" : ", none") + "> + cg_direction_blocks";
+
+  // setup: the inverse blocks, r = b - A x0, the sums and the states, the stop word
+  const dev::SolveBlocks v = S.blocks();
+  const dim3 parts = grid(S.total[dev::BLOCKS_PARTS]);
+  if (S.pre) {
+    e = with_block(S, [&](auto BS, auto, auto) {
+      if (!S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_csr_blocks_kernel<BS()>), parts, dim3(256), 0, S.s, S.P.a, v.B, S.dinv, S.part_bad);
+      if constexpr (BS() == 3 || BS() == 4)
+        if (S.dinv_tile) hipLaunchKernelGGL((dev::solve_dinv_tile_blocks_kernel<BS(), BS()>), parts, dim3(256), 0, S.s, S.P.a, v.B, S.dinv, S.part_bad);
+      return hipGetLastError();
+    });
+    if (e != hipSuccess) return hip_fail(e, E.who);
+  }
+  if (S.x0)
+    if (int rc = hdd::abi::run_apply_blocks(E.who, ctx, S.P, S.tab, n_blocks, S.total[dev::BLOCKS_APPLY], S.x, S.q, S.s)) return rc;
+  e = with_block(S, [&](auto BS, auto PRE, auto A16) {
+    hipLaunchKernelGGL((dev::cg_init_blocks_kernel<BS(), PRE(), A16()>), parts, dim3(256), 0, S.s, v, d_b, S.x0);
+    return hipGetLastError();
+  });
+  if (e != hipSuccess) return hip_fail(e, E.who);
+  hipLaunchKernelGGL(dev::cg_init_state_blocks_kernel, grid(n_blocks), dim3(64), 0, S.s, v, S.pre, opt->rtol, opt->atol);
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, E.who);
+  hipLaunchKernelGGL(dev::cg_stop_blocks_kernel, dim3(1), dim3(256), 0, S.s, S.state, n_blocks, S.stop);   // the first value of the stop word
+  if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, E.who);
+
+  // the iterations; a look: the stop word alone
+  dev::ApplyArgs a = S.P.a;
+  a.nv = 1;
+  a.x = S.p;
+  a.y = S.q;
+  a.ldx = a.ldy = S.ldw;
+  a.partial = S.part_pq;
+  a.done_at = nullptr;   // the segments' are in the table's view
+  const dev::BlocksArgs dot = S.blocks_args(dev::BLOCKS_DOT);
+  const int every = opt->check_every > 0 ? opt->check_every : 32;
+  const int32_t* stop_h = reinterpret_cast<const int32_t*>(ctx->solve_state_h);
+  int k = 0;
+  for (;;) {
+    const int batch = std::min(every, opt->max_iter - k);
+    for (int i = 0; i < batch; ++i, ++k) {
+      a.iteration = k;
+      e = hdd::abi::launch_apply_blocks<true>(S.P, a, dot, S.total[dev::BLOCKS_DOT], S.s);
+      if (e != hipSuccess) return hip_fail(e, E.who);
+      e = with_block(S, [&](auto BS, auto PRE, auto A16) {
+        hipLaunchKernelGGL((dev::cg_update_blocks_kernel<BS(), PRE(), A16()>), grid(S.total[dev::BLOCKS_PARTS] + 1), dim3(256), 0, S.s, v, k);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(dev::cg_direction_blocks_kernel<PRE()>, grid(S.total[dev::BLOCKS_DIRECTION]), dim3(256), 0, S.s, v, k);
+        return hipGetLastError();
+      });
+      if (e != hipSuccess) return hip_fail(e, E.who);
+    }
+    hipLaunchKernelGGL(dev::cg_stop_blocks_kernel, dim3(1), dim3(256), 0, S.s, S.state, n_blocks, S.stop);
+    e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->solve_state_h, S.stop, 64, hipMemcpyDeviceToHost, S.s);
+    if (e == hipSuccess) e = hipStreamSynchronize(S.s);
+    if (e != hipSuccess) return hip_fail(e, E.who);
+    if (*stop_h <= k || k >= opt->max_iter) break;
+  }
+
+  // the states of all segments, once; b_s = 0: x_s = 0 whatever the initial guess was
+  e = hipMemcpyAsync(ctx->solve_state_h, S.state, size_t(n_blocks) * sizeof(dev::SolveState), hipMemcpyDeviceToHost, S.s);
+  if (e == hipSuccess) e = hipStreamSynchronize(S.s);
+  const dev::SolveState* h = reinterpret_cast<const dev::SolveState*>(ctx->solve_state_h);
+  bool cleared = false;
+  for (int c = 0; c < n_blocks && e == hipSuccess; ++c) {
+    info[c] = hdd_solve_info{h[c].done_at <= k ? h[c].status : HDD_SOLVE_MAX_ITER, h[c].iteration, std::sqrt(h[c].rr), std::sqrt(h[c].bb)};
+    if (h[c].flags & dev::SOLVE_FLAG_ZERO_RHS) {
+      e = hipMemsetAsync(S.x + (bounds[c] - bounds[0]), 0, size_t(bounds[c + 1] - bounds[c]) * sizeof(double), S.s);
+      info[c].residual = 0.0;
+      cleared = true;
+    }
+  }
+  if (cleared && e == hipSuccess) e = hipStreamSynchronize(S.s);
+  return e == hipSuccess ? HDD_OK : hip_fail(e, E.who);
 }

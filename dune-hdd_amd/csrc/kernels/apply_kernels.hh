@@ -82,6 +82,60 @@ struct ApplyMultiArgs {
   double theta[APPLY_NV][HDD_MAX_COMP];
 };
 
+// What one workgroup sees of a launch: its index w() in a grid of nw() workgroups (a Grid), and the ranges and the
+// vectors (a View).  A plain launch passes its own blockIdx.x / gridDim.x (LaunchGrid, read where they are used,
+// as the kernels always did) and the plan's fields (PlanView); a blocks launch (hdd_operator_apply_blocks /
+// _solve_blocks, the end of this file) the virtual index and grid of the workgroup's segment (VirtualGrid) and the
+// segment's (SegmentView) ranges, vector offsets, partial sums and stop word.  Every order of summation in the bodies is a function
+// of (w, nw) and the ranges alone.
+struct LaunchGrid {
+  __device__ __forceinline__ uint32_t w() const { return blockIdx.x; }
+  __device__ __forceinline__ uint32_t nw() const { return gridDim.x; }
+};
+struct VirtualGrid {
+  uint32_t w_, nw_;
+  __device__ __forceinline__ uint32_t w() const { return w_; }
+  __device__ __forceinline__ uint32_t nw() const { return nw_; }
+};
+
+// the plan's own fields, read where they are used
+struct PlanView {
+  const ApplyArgs& a;
+  __device__ __forceinline__ int64_t e_begin() const { return a.e_begin; }
+  __device__ __forceinline__ int64_t e_end() const { return a.e_end; }
+  __device__ __forceinline__ int64_t ce_begin() const { return a.ce_begin; }
+  __device__ __forceinline__ int64_t ce_end() const { return a.ce_end; }
+  __device__ __forceinline__ int64_t row_begin() const { return a.row_begin; }
+  __device__ __forceinline__ int64_t row_end() const { return a.row_end; }
+  __device__ __forceinline__ int64_t col_begin() const { return a.col_begin; }
+  __device__ __forceinline__ int64_t col_end() const { return a.col_end; }
+  __device__ __forceinline__ const double* x() const { return a.x; }
+  __device__ __forceinline__ double* y() const { return a.y; }
+  __device__ __forceinline__ double* partial() const { return a.partial; }
+  __device__ __forceinline__ const int32_t* done_at() const { return a.done_at; }
+};
+__device__ __forceinline__ PlanView apply_view(const ApplyArgs& a) { return PlanView{a}; }
+
+// a segment's
+struct SegmentView {
+  int64_t e_begin_, e_end_, ce_begin_, ce_end_, row_begin_, row_end_;
+  const double* x_;
+  double *y_, *partial_;
+  const int32_t* done_at_;
+  __device__ __forceinline__ int64_t e_begin() const { return e_begin_; }
+  __device__ __forceinline__ int64_t e_end() const { return e_end_; }
+  __device__ __forceinline__ int64_t ce_begin() const { return ce_begin_; }
+  __device__ __forceinline__ int64_t ce_end() const { return ce_end_; }
+  __device__ __forceinline__ int64_t row_begin() const { return row_begin_; }
+  __device__ __forceinline__ int64_t row_end() const { return row_end_; }
+  __device__ __forceinline__ int64_t col_begin() const { return row_begin_; }   // square and diagonal
+  __device__ __forceinline__ int64_t col_end() const { return row_end_; }
+  __device__ __forceinline__ const double* x() const { return x_; }
+  __device__ __forceinline__ double* y() const { return y_; }
+  __device__ __forceinline__ double* partial() const { return partial_; }
+  __device__ __forceinline__ const int32_t* done_at() const { return done_at_; }
+};
+
 // sizes of the tile kernel's LDS image: 16-byte chunks per lane (odd row blocks, P1: the image origin may lie one
 // value in front of the tile) and how many of them are loaded back to back
 template <int NB, int NF>
@@ -146,8 +200,8 @@ __device__ __forceinline__ double apply_wave_sum(double s)
 }
 
 // The tile algorithm (header comment).  NC = 0: theta[0] for all vectors; NC >= 1: theta[v] for vector v, NC = n_comp.
-template <int NB, int NF, int NV, bool DOT, int NC>
-__device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double (*theta)[HDD_MAX_COMP], int64_t n_tiles)
+template <int NB, int NF, int NV, bool DOT, int NC, class View, class Grid>
+__device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const View& g, const Grid& grid, const double (*theta)[HDD_MAX_COMP], int64_t n_tiles)
 {
   using I = ApplyImage<NB, NF>;
   constexpr int CH = I::CHUNKS, U = I::U, IMG = I::BYTES / 8;
@@ -156,20 +210,20 @@ __device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double
   const int lane = threadIdx.x;
   [[maybe_unused]] double dot[NV] = {};   // DOT: this lane's x_v . y_v over its elements, in tile order
   if constexpr (DOT)
-    if (*a.done_at <= a.iteration) return;   // (wave-uniform)
-  const TileRange r = tile_range(blockIdx.x, gridDim.x, n_tiles);
-  const uint32_t xbytes = uint32_t((a.ce_end - a.ce_begin) * NB * 8);
+    if (*g.done_at() <= a.iteration) return;   // (wave-uniform)
+  const TileRange r = tile_range(grid.w(), grid.nw(), n_tiles);
+  const uint32_t xbytes = uint32_t((g.ce_end() - g.ce_begin()) * NB * 8);
   __amdgpu_buffer_rsrc_t xr[NV];
   [[maybe_unused]] double th[NT][HDD_MAX_COMP];   // NC >= 1: the thetas in registers (entries [.][< NC])
 #pragma unroll
   for (int v = 0; v < NV; ++v) {
-    xr[v] = apply_rsrc(a.x + (v < a.nv ? v : 0) * a.ldx, xbytes);
+    xr[v] = apply_rsrc(g.x() + (v < a.nv ? v : 0) * a.ldx, xbytes);
 #pragma unroll
     for (int q = 0; q < NC; ++q) th[v][q] = theta[v][q];
   }
   for (int64_t t = r.t; t < r.t_end; t += r.t_step) {
-    const int64_t t0 = a.e_begin + t * 64;
-    const int64_t tend = t0 + 64 < a.e_end ? t0 + 64 : a.e_end;
+    const int64_t t0 = g.e_begin() + t * 64;
+    const int64_t tend = t0 + 64 < g.e_end() ? t0 + 64 : g.e_end();
     const bool active = t0 + lane < tend;
     const int64_t e = active ? t0 + lane : t0;
     int nbr[NF];
@@ -259,8 +313,8 @@ __device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double
       for (int i = 0; i < NB; ++i) acc[v][i] = 0.0;
 #pragma unroll
     for (int b = 0; b <= NF; ++b) {
-      if (b > nint || id[b] < a.ce_begin || id[b] >= a.ce_end) continue;   // skipped, not multiplied by zero
-      const uint32_t xo = uint32_t(id[b] - int(a.ce_begin)) * uint32_t(NB * 8);
+      if (b > nint || id[b] < g.ce_begin() || id[b] >= g.ce_end()) continue;   // skipped, not multiplied by zero
+      const uint32_t xo = uint32_t(id[b] - int(g.ce_begin())) * uint32_t(NB * 8);
       double xv[NV][NB];
 #pragma unroll
       for (int v = 0; v < NV; ++v)
@@ -290,7 +344,7 @@ __device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double
           }
         }
     }
-    double* yo = a.y + (e - a.e_begin) * NB;
+    double* yo = g.y() + (e - g.e_begin()) * NB;
 #pragma unroll
     for (int v = 0; v < NV; ++v)
       if (v < a.nv)
@@ -306,7 +360,7 @@ __device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
       dot[v] = apply_wave_sum(dot[v]);
-      if (lane == 0 && v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = dot[v];
+      if (lane == 0 && v < a.nv) g.partial()[int64_t(v) * grid.nw() + grid.w()] = dot[v];
     }
   }
 }
@@ -314,29 +368,29 @@ __device__ __forceinline__ void apply_tile_body(const ApplyArgs& a, const double
 template <int NB, int NF, int NV, bool DOT = false>
 __global__ void __launch_bounds__(64) apply_tile_kernel(const ApplyArgs a, int64_t n_tiles)
 {
-  apply_tile_body<NB, NF, NV, DOT, 0>(a, &a.theta, n_tiles);
+  apply_tile_body<NB, NF, NV, DOT, 0>(a, apply_view(a), LaunchGrid{}, &a.theta, n_tiles);
 }
 
 template <int NB, int NF, int NV, bool DOT, int NC>
 __global__ void __launch_bounds__(64) apply_tile_multi_kernel(const ApplyMultiArgs ma, int64_t n_tiles)
 {
   static_assert(NV <= APPLY_NV && NC >= 1 && NC <= HDD_MAX_COMP, "theta[APPLY_NV][HDD_MAX_COMP]");
-  apply_tile_body<NB, NF, NV, DOT, NC>(ma.a, ma.theta, n_tiles);
+  apply_tile_body<NB, NF, NV, DOT, NC>(ma.a, apply_view(ma.a), LaunchGrid{}, ma.theta, n_tiles);
 }
 
 // The CSR algorithm: G lanes per row, 256 / G rows per workgroup pass.  NT = 1: theta[0] for all vectors; NT = NV:
 // theta[v] for vector v.
-template <int G, int NV, bool DOT, int NT>
-__device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const double (*theta)[HDD_MAX_COMP])
+template <int G, int NV, bool DOT, int NT, class View, class Grid>
+__device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const View& g, const Grid& grid, const double (*theta)[HDD_MAX_COMP])
 {
   [[maybe_unused]] double dot[NV] = {};   // DOT: the group leaders' x_r y_r over their rows, in row order
   if constexpr (DOT)
-    if (*a.done_at <= a.iteration) return;   // (uniform)
+    if (*g.done_at() <= a.iteration) return;   // (uniform)
   const int gl = threadIdx.x % G;
-  const int64_t n_rows = a.row_end - a.row_begin;
-  const int64_t stride = int64_t(gridDim.x) * (256 / G);
-  for (int64_t rr = int64_t(blockIdx.x) * (256 / G) + threadIdx.x / G; rr < n_rows; rr += stride) {
-    int64_t k0 = a.row_ptr[a.row_begin + rr], k1 = a.row_ptr[a.row_begin + rr + 1];
+  const int64_t n_rows = g.row_end() - g.row_begin();
+  const int64_t stride = int64_t(grid.nw()) * (256 / G);
+  for (int64_t rr = int64_t(grid.w()) * (256 / G) + threadIdx.x / G; rr < n_rows; rr += stride) {
+    int64_t k0 = a.row_ptr[g.row_begin() + rr], k1 = a.row_ptr[g.row_begin() + rr + 1];
     k0 = k0 < 0 ? 0 : k0;
     k1 = k1 > a.nnz ? a.nnz : k1;
     double acc[NV];
@@ -344,10 +398,10 @@ __device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const double 
     for (int v = 0; v < NV; ++v) acc[v] = 0.0;
     for (int64_t k = k0 + gl; k < k1; k += G) {
       const int64_t c = a.col[k];
-      if (c < a.col_begin || c >= a.col_end) continue;   // skipped, not multiplied by zero
+      if (c < g.col_begin() || c >= g.col_end()) continue;   // skipped, not multiplied by zero
       double m[NT];
       apply_entries<NT>(m, theta, a.n_comp, [&](int q) { return a.vals[q][k]; });
-      const double* xc = a.x + (c - a.col_begin);
+      const double* xc = g.x() + (c - g.col_begin());
 #pragma unroll
       for (int v = 0; v < NV; ++v)
         if (v < a.nv) acc[v] = __builtin_fma(m[NT == 1 ? 0 : v], xc[v * a.ldx], acc[v]);
@@ -359,12 +413,12 @@ __device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const double 
     if (gl == 0)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        if (v < a.nv) a.y[v * a.ldy + rr] = acc[v];
+        if (v < a.nv) g.y()[v * a.ldy + rr] = acc[v];
     if constexpr (DOT)
       if (gl == 0)   // square diagonal range: row rr is column rr
 #pragma unroll
         for (int v = 0; v < NV; ++v)
-          if (v < a.nv) dot[v] = __builtin_fma(a.x[v * a.ldx + rr], acc[v], dot[v]);
+          if (v < a.nv) dot[v] = __builtin_fma(g.x()[v * a.ldx + rr], acc[v], dot[v]);
   }
   if constexpr (DOT) {
     __shared__ double red[NV][4];
@@ -377,21 +431,93 @@ __device__ __forceinline__ void apply_csr_body(const ApplyArgs& a, const double 
     if (threadIdx.x == 0)
 #pragma unroll
       for (int v = 0; v < NV; ++v)
-        if (v < a.nv) a.partial[int64_t(v) * gridDim.x + blockIdx.x] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
+        if (v < a.nv) g.partial()[int64_t(v) * grid.nw() + grid.w()] = ((red[v][0] + red[v][1]) + red[v][2]) + red[v][3];
   }
 }
 
 template <int G, int NV, bool DOT = false>
 __global__ void __launch_bounds__(256) apply_csr_kernel(const ApplyArgs a)
 {
-  apply_csr_body<G, NV, DOT, 1>(a, &a.theta);
+  apply_csr_body<G, NV, DOT, 1>(a, apply_view(a), LaunchGrid{}, &a.theta);
 }
 
 template <int G, int NV, bool DOT = false>
 __global__ void __launch_bounds__(256) apply_csr_multi_kernel(const ApplyMultiArgs ma)
 {
   static_assert(NV <= APPLY_NV, "theta[APPLY_NV][HDD_MAX_COMP]");
-  apply_csr_body<G, NV, DOT, NV>(ma.a, ma.theta);
+  apply_csr_body<G, NV, DOT, NV>(ma.a, apply_view(ma.a), LaunchGrid{}, ma.theta);
+}
+
+// ---- the block-diagonal part with respect to row segments (hdd_operator_apply_blocks / _solve_blocks) -------------
+// One launch serves every segment [row_begin, row_begin + rows) of a partition of a row interval: segment s gets the
+// virtual grid grid[kind] it would have in a launch of its own (kind: which launch of the solve, BLOCKS_*), the
+// launch has the sum of them as real workgroups, and real workgroup b belongs to the segment s with first[kind] <= b
+// < first[kind] + grid[kind], as its virtual workgroup b - first[kind].  The host builds the table (64 bytes per
+// segment); a workgroup finds its segment by bisection over first[kind] -- wave-uniform, so scalar loads: twelve
+// steps at the most (HDD_MAX_SOLVE_BLOCKS segments), which need no table entry per workgroup and no second copy to
+// the device.  (A per-workgroup table was not measured against it.)
+enum { BLOCKS_DOT = 0, BLOCKS_PARTS = 1, BLOCKS_DIRECTION = 2, BLOCKS_APPLY = 3, BLOCKS_KINDS = 4 };
+
+struct BlockSegment {
+  int64_t row_begin, rows;           // rows = columns of the matrix
+  int64_t e_begin, e_end;            // tile path: local element ids of the rows
+  int32_t first[BLOCKS_KINDS];       // per kind of launch: the segment's first real workgroup; also the offset of its
+  int32_t grid[BLOCKS_KINDS];        //   partial sums of that kind; and its virtual grid
+};
+static_assert(sizeof(BlockSegment) == 64, "eight doubles of the workspace");
+
+struct BlocksArgs {
+  const BlockSegment* seg;
+  int32_t n_seg, kind;
+  int64_t row0;                      // first row of the interval: segment s of a vector sits at row_begin - row0
+  const int32_t* stop;               // DOT: the call's stop word
+  const int32_t* done_at;            // DOT: segment s's stop word at done_at[16 s] (its 64-byte SolveState)
+};
+
+// the segment of real workgroup b: the last s with first[kind] <= b (the grids are positive: first ascends strictly)
+__device__ __forceinline__ int blocks_find(const BlockSegment* seg, int n_seg, int kind, uint32_t b)
+{
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (uint32_t(seg[mid].first[kind]) <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// segment s as the bodies see it from real workgroup blockIdx.x: x, y and partial are the interval's
+__device__ __forceinline__ VirtualGrid blocks_grid(const BlockSegment& g, int kind)
+{
+  return VirtualGrid{blockIdx.x - uint32_t(g.first[kind]), uint32_t(g.grid[kind])};
+}
+__device__ __forceinline__ SegmentView blocks_view(const ApplyArgs& a, const BlocksArgs& B, int s)
+{
+  const BlockSegment& g = B.seg[s];
+  const int64_t o = g.row_begin - B.row0;
+  return SegmentView{g.e_begin, g.e_end, g.e_begin - a.own_begin, g.e_end - a.own_begin, g.row_begin, g.row_begin + g.rows,
+                     a.x + o, a.y + o, a.partial + g.first[B.kind], B.done_at + 16 * int64_t(s)};
+}
+
+// One vector.  DOT: the call's stop word first, then (in the body) the segment's: a workgroup of a segment that is
+// done returns at once.
+template <int NB, int NF, bool DOT = false>
+__global__ void __launch_bounds__(64) apply_tile_blocks_kernel(const ApplyArgs a, const BlocksArgs B)
+{
+  if constexpr (DOT)
+    if (*B.stop <= a.iteration) return;   // (uniform)
+  const int s = blocks_find(B.seg, B.n_seg, B.kind, blockIdx.x);
+  const SegmentView g = blocks_view(a, B, s);
+  apply_tile_body<NB, NF, 1, DOT, 0>(a, g, blocks_grid(B.seg[s], B.kind), &a.theta, (g.e_end() - g.e_begin() + 63) / 64);
+}
+
+template <int G, bool DOT = false>
+__global__ void __launch_bounds__(256) apply_csr_blocks_kernel(const ApplyArgs a, const BlocksArgs B)
+{
+  if constexpr (DOT)
+    if (*B.stop <= a.iteration) return;   // (uniform)
+  const int s = blocks_find(B.seg, B.n_seg, B.kind, blockIdx.x);
+  apply_csr_body<G, 1, DOT, 1>(a, blocks_view(a, B, s), blocks_grid(B.seg[s], B.kind), &a.theta);
 }
 
 // apply2, stage 1: partial[block][i * HDD_MAX_VEC + j] = sum over the block's rows of v_i[r] w_j[r] (fixed row ->

@@ -1,6 +1,6 @@
 // dune-hdd_amd/csrc/kernels/apply_plan.hh -- the checked plan of an operator application (internal): what
 // hdd_operator_apply / _apply_multi / _apply2 (abi_apply.hip, which defines the functions declared here) and
-// hdd_operator_solve[_batched / _multi] (abi_solve.hip) share, so that the operator arguments are checked in one
+// hdd_operator_solve[_batched / _multi / _blocks] (abi_solve.hip) share, so that the operator arguments are checked in one
 // place (plan_apply) and every apply kernel is launched from one place (launch_apply).
 #pragma once
 #include <algorithm>
@@ -109,6 +109,45 @@ hipError_t launch_apply(const ApplyPlan& P, const Args& args, int64_t grid, hipS
     csr(integral_constant<int, 64>{});
   return hipGetLastError();
 }
+
+// ---- the block-diagonal part with respect to row segments (hdd_operator_apply_blocks / _solve_blocks) -------------
+
+// The checks of n_blocks and bounds (host [n_blocks + 1]), then plan_apply on the square range of the whole interval
+// (bounds[0], bounds[n_blocks]).  The tile kernel only where every bound is a multiple of nb -- where the single call
+// on every segment's range would take it; else the CSR kernel, whose arrays the pattern must then have.
+int plan_blocks(const char* who, hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds, ApplyPlan& P);
+
+// The table of a checked blocks plan (dev::BlockSegment, host memory [n_blocks]): per segment the ranges and, per kind
+// of launch, the grid a call on the segment alone has (BLOCKS_APPLY: apply_grid, BLOCKS_DOT: dot_grid with max_parts;
+// with block_size > 0 also the solve's update and direction grids, else 1) and their prefix sums.  total: the real
+// workgroups of a launch of each kind.
+void blocks_table(const hdd_ctx* ctx, const ApplyPlan& P, int32_t n_blocks, const int64_t* bounds, int block_size, int64_t max_parts,
+                  dev::BlockSegment* tab, int64_t (&total)[dev::BLOCKS_KINDS]);
+
+// "apply_tile_blocks_kernel<3, 3, dot>", "apply_csr_blocks_kernel<8>", ... appended to out
+void apply_blocks_kernel_name(std::string& out, const ApplyPlan& P, bool dot);
+
+// One launch for every segment of the table at B.seg (device), `grid` = total[B.kind] workgroups, one vector
+template <bool DOT>
+hipError_t launch_apply_blocks(const ApplyPlan& P, const dev::ApplyArgs& a, const dev::BlocksArgs& B, int64_t grid, hipStream_t s)
+{
+  const dim3 g{unsigned(grid)};
+  if (P.tile && P.nb == 3)
+    hipLaunchKernelGGL((dev::apply_tile_blocks_kernel<3, 3, DOT>), g, dim3(64), (dev::ApplyImage<3, 3>::BYTES), s, a, B);
+  else if (P.tile)
+    hipLaunchKernelGGL((dev::apply_tile_blocks_kernel<4, 4, DOT>), g, dim3(64), (dev::ApplyImage<4, 4>::BYTES), s, a, B);
+  else if (P.short_rows)
+    hipLaunchKernelGGL((dev::apply_csr_blocks_kernel<8, DOT>), g, dim3(256), 0, s, a, B);
+  else
+    hipLaunchKernelGGL((dev::apply_csr_blocks_kernel<64, DOT>), g, dim3(256), 0, s, a, B);
+  return hipGetLastError();
+}
+
+// y_s = A_ss x_s for every segment: the plain launch (kind BLOCKS_APPLY) on the device table d_tab; x, y are the
+// interval's vectors.  Names the kernel for hdd_last_apply_kernel().
+int run_apply_blocks(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const dev::BlockSegment* d_tab, int32_t n_blocks, int64_t grid,
+                     const double* d_x, double* d_y, void* stream);
 
 }  // namespace abi
 }  // namespace hdd

@@ -80,7 +80,15 @@ struct hdd_ctx {
   // hdd_operator_solve[_batched]: pinned host bytes the device state is read back into -- one 64-byte state per
   // column (HDD_MAX_VEC of them) and 64 bytes of group stop words behind them
   static constexpr size_t SOLVE_STATE_BYTES = (HDD_MAX_VEC + 1) * 64;
-  double* solve_state_h = nullptr;
+  // hdd_operator_solve_blocks reads one state per segment back into the same buffer at the end of a call
+  static constexpr size_t SOLVE_BLOCKS_BYTES = size_t(HDD_MAX_SOLVE_BLOCKS) * 64;
+  double* solve_state_h = nullptr;   // SOLVE_BLOCKS_BYTES (the larger)
+  // hdd_operator_apply_blocks / _solve_blocks: the segment table (64 bytes per segment) is built in pinned host
+  // memory; the apply, which has no workspace, keeps its device copy here.  The event is recorded behind the upload:
+  // the next call waits for it before it overwrites the host table.
+  void* blocks_tab_h = nullptr;
+  void* blocks_tab_d = nullptr;
+  hipEvent_t blocks_evt = nullptr;
 
   // the scratch buffers release themselves; what is left are the plain members
   ~hdd_ctx()
@@ -88,6 +96,9 @@ struct hdd_ctx {
     if (q3g_tab) (void)hipFree(q3g_tab);
     if (apply2_ws) (void)hipFree(apply2_ws);
     if (solve_state_h) (void)hipHostFree(solve_state_h);
+    if (blocks_tab_h) (void)hipHostFree(blocks_tab_h);
+    if (blocks_tab_d) (void)hipFree(blocks_tab_d);
+    if (blocks_evt) (void)hipEventDestroy(blocks_evt);
     if (nnz_h) (void)hipHostFree(nnz_h);
     if (rhs_evt) (void)hipEventDestroy(rhs_evt);
     if (ops_evt) (void)hipEventDestroy(ops_evt);

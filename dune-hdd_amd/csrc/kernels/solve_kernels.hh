@@ -187,14 +187,15 @@ __device__ __forceinline__ bool solve_invert(double (&A)[BS][BS], double* out)
 // Diagonal blocks on the tile path (BS == NB): lane = element.  Its own block is block number (interior neighbours
 // with a smaller id) of its row block, whose row stride is NB (interior neighbours + 1) -- from elem_ptr and the
 // neighbours alone; col is not read.  part_bad[workgroup] = blocks that were not positive definite.
-template <int NB, int NF>
-__global__ void __launch_bounds__(256) solve_dinv_tile_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+// g: the workgroup's view (apply_kernels.hh) -- its index, the grid and the element range; dinv, part_bad: the range's;
+// red: four doubles of the kernel's LDS
+template <int NB, int NF, class View, class Grid>
+__device__ __forceinline__ void solve_dinv_tile_body(const ApplyArgs& a, const View& g, const Grid& grid, double* dinv, double* part_bad, double* red)
 {
-  __shared__ double red[4];
   double bad = 0.0;
-  const int64_t n_el = a.e_end - a.e_begin;
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_el; i += int64_t(gridDim.x) * 256) {
-    const int64_t e = a.e_begin + i;
+  const int64_t n_el = g.e_end() - g.e_begin();
+  for (int64_t i = int64_t(grid.w()) * 256 + threadIdx.x; i < n_el; i += int64_t(grid.nw()) * 256) {
+    const int64_t e = g.e_begin() + i;
     int nint = 0, pos = 0;
 #pragma unroll
     for (int f = 0; f < NF; ++f) {
@@ -216,18 +217,24 @@ __global__ void __launch_bounds__(256) solve_dinv_tile_kernel(const ApplyArgs a,
     if (!solve_invert<NB>(D, dinv + i * solve_packed<NB>())) bad += 1.0;
   }
   const double s = solve_block_sum(bad, red);
-  if (threadIdx.x == 0) part_bad[blockIdx.x] = s;
+  if (threadIdx.x == 0) part_bad[grid.w()] = s;
+}
+
+template <int NB, int NF>
+__global__ void __launch_bounds__(256) solve_dinv_tile_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+{
+  __shared__ double red[4];
+  solve_dinv_tile_body<NB, NF>(a, apply_view(a), LaunchGrid{}, dinv, part_bad, red);
 }
 
 // Diagonal blocks on the CSR path: thread = block of BS rows, found in col
-template <int BS>
-__global__ void __launch_bounds__(256) solve_dinv_csr_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+template <int BS, class View, class Grid>
+__device__ __forceinline__ void solve_dinv_csr_body(const ApplyArgs& a, const View& g, const Grid& grid, double* dinv, double* part_bad, double* red)
 {
-  __shared__ double red[4];
   double bad = 0.0;
-  const int64_t n_blk = (a.row_end - a.row_begin) / BS;
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
-    const int64_t r0 = a.row_begin + i * BS;
+  const int64_t n_blk = (g.row_end() - g.row_begin()) / BS;
+  for (int64_t i = int64_t(grid.w()) * 256 + threadIdx.x; i < n_blk; i += int64_t(grid.nw()) * 256) {
+    const int64_t r0 = g.row_begin() + i * BS;
     double D[BS][BS];
 #pragma unroll
     for (int r = 0; r < BS; ++r) {
@@ -248,17 +255,24 @@ __global__ void __launch_bounds__(256) solve_dinv_csr_kernel(const ApplyArgs a, 
     if (!solve_invert<BS>(D, dinv + i * solve_packed<BS>())) bad += 1.0;
   }
   const double s = solve_block_sum(bad, red);
-  if (threadIdx.x == 0) part_bad[blockIdx.x] = s;
+  if (threadIdx.x == 0) part_bad[grid.w()] = s;
+}
+
+template <int BS>
+__global__ void __launch_bounds__(256) solve_dinv_csr_kernel(const ApplyArgs a, double* dinv, double* part_bad)
+{
+  __shared__ double red[4];
+  solve_dinv_csr_body<BS>(a, apply_view(a), LaunchGrid{}, dinv, part_bad, red);
 }
 
 // Setup: r = b (X0: b - q, q = A x0 from a plain apply), x = 0 (X0: kept), z = D^-1 r, p = z; partials of b.b, r.z, r.r
-template <int BS, bool PRE, bool A16>
-__global__ void __launch_bounds__(256) cg_init_kernel(const SolveVectors v, const double* b, bool x0)
+// (grid: the launch's own, or the virtual ones of a segment; red: the kernel's LDS)
+template <int BS, bool PRE, bool A16, class Grid>
+__device__ __forceinline__ void cg_init_body(const SolveVectors& v, const double* b, bool x0, const Grid& grid, double (&red)[3][4])
 {
-  __shared__ double red[3][4];
   double bb = 0.0, rz = 0.0, rr = 0.0;
   const int64_t n_blk = v.n / BS;
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+  for (int64_t i = int64_t(grid.w()) * 256 + threadIdx.x; i < n_blk; i += int64_t(grid.nw()) * 256) {
     const int64_t o = i * BS;
     double bv[BS], rv[BS], zv[BS];
 #pragma unroll
@@ -287,10 +301,17 @@ __global__ void __launch_bounds__(256) cg_init_kernel(const SolveVectors v, cons
   }
   const double s0 = solve_block_sum(bb, red[0]), s1 = solve_block_sum(rz, red[1]), s2 = solve_block_sum(rr, red[2]);
   if (threadIdx.x == 0) {
-    v.part_bb[blockIdx.x] = s0;
-    v.part_rz[blockIdx.x] = s1;
-    v.part_rr[blockIdx.x] = s2;
+    v.part_bb[grid.w()] = s0;
+    v.part_rz[grid.w()] = s1;
+    v.part_rr[grid.w()] = s2;
   }
+}
+
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_init_kernel(const SolveVectors v, const double* b, bool x0)
+{
+  __shared__ double red[3][4];
+  cg_init_body<BS, PRE, A16>(v, b, x0, LaunchGrid{}, red);
 }
 
 // One column's state before the first iteration and history[0] (nullable), by one lane; bad: the number of
@@ -357,17 +378,16 @@ __device__ __forceinline__ void solve_update_block(const double* p, const double
   if constexpr (PRE) solve_store<BS, A16>(z, zv);
 }
 
-template <int BS, bool PRE, bool A16>
-__global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, int k)
+template <int BS, bool PRE, bool A16, class Grid>
+__device__ __forceinline__ void cg_update_body(const SolveVectors& v, int k, const Grid& grid, double (&red)[2][4])
 {
-  __shared__ double red[2][4];
   if (v.state->done_at <= k) return;   // (uniform)
   const double pq = solve_wave_sum(v.part_pq, v.n_pq);
   if (!solve_finite(pq) || !(pq > 0.0)) return;   // breakdown: cg_direction_kernel sees the same sum and records it
   const double alpha = v.state->rho[k & 1] / pq;
   double rz = 0.0, rr = 0.0;
   const int64_t n_blk = v.n / BS;
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n_blk; i += int64_t(gridDim.x) * 256) {
+  for (int64_t i = int64_t(grid.w()) * 256 + threadIdx.x; i < n_blk; i += int64_t(grid.nw()) * 256) {
     const int64_t o = i * BS;
     [[maybe_unused]] double m[solve_packed<BS>()];
     if constexpr (PRE) solve_load_packed<BS>(v.dinv + i * solve_packed<BS>(), m);
@@ -375,23 +395,31 @@ __global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, in
   }
   const double s0 = solve_block_sum(rz, red[0]), s1 = solve_block_sum(rr, red[1]);
   if (threadIdx.x == 0) {
-    if constexpr (PRE) v.part_rz[blockIdx.x] = s0;
-    v.part_rr[blockIdx.x] = s1;
+    if constexpr (PRE) v.part_rz[grid.w()] = s0;
+    v.part_rr[grid.w()] = s1;
   }
+}
+
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_update_kernel(const SolveVectors v, int k)
+{
+  __shared__ double red[2][4];
+  cg_update_body<BS, PRE, A16>(v, k, LaunchGrid{}, red);
 }
 
 // The end of iteration k for one column that was live (done_at > k) when the launch began: sums the partials
 // (n_parts: workgroups of the cg_update launch), decides, p = z + beta p; the writer (one lane of the launch) stores
-// the state and history[k + 1] (history: the column's, nullable).  Returns the column's done_at after this launch:
+// the state and history[k + 1] (history: the column's, nullable); workgroup grid.w() of grid.nw() (the launch's own, or the virtual
+// ones of a segment: the update of p has no sum in it, so its grid is free).  Returns the column's done_at after this launch:
 // k (p . q breakdown: x, r are those of iteration k), k + 1 (converged / r . z breakdown) or SOLVE_RUNNING.
 // The other workgroups of launch k read done_at while the writer stores it, and decide the same for the old value
 // SOLVE_RUNNING and for the new one: `<= k` is false for k + 1 as well; and a reader of the old value before a new k
 // forms the same p . q from the same partial sums and leaves the column alone, too.  The launches before (apply,
 // update of iteration k) and after (iteration k + 1) are ordered by the stream.
-template <bool PRE>
+template <bool PRE, class Grid>
 __device__ __forceinline__ int solve_direction_column(SolveState& s, const double* part_pq, int n_pq, const double* part_rz,
                                                       const double* part_rr, int n_parts, double* p, const double* z, int64_t n,
-                                                      double* history, int k, bool writer)
+                                                      double* history, int k, bool writer, const Grid& grid)
 {
   const double pq = solve_wave_sum(part_pq, n_pq);
   if (!solve_finite(pq) || !(pq > 0.0)) {
@@ -412,7 +440,7 @@ __device__ __forceinline__ int solve_direction_column(SolveState& s, const doubl
   }
   if (converged || broken) return k + 1;
   const double beta = rz / s.rho[k & 1];
-  for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n; i += int64_t(gridDim.x) * 256)
+  for (int64_t i = int64_t(grid.w()) * 256 + threadIdx.x; i < n; i += int64_t(grid.nw()) * 256)
     p[i] = __builtin_fma(beta, p[i], z[i]);
   return SOLVE_RUNNING;
 }
@@ -422,7 +450,7 @@ __global__ void __launch_bounds__(256) cg_direction_kernel(const SolveVectors v,
 {
   if (v.state->done_at <= k) return;   // (uniform)
   solve_direction_column<PRE>(*v.state, v.part_pq, v.n_pq, v.part_rz, v.part_rr, n_parts, v.p, v.z, v.n, v.history, k,
-                              blockIdx.x == 0 && threadIdx.x == 0);
+                              blockIdx.x == 0 && threadIdx.x == 0, LaunchGrid{});
 }
 
 // ---- several right-hand sides per call (hdd_operator_solve_batched) ----------------------------------------------
@@ -546,11 +574,153 @@ __global__ void __launch_bounds__(256) cg_direction_batched_kernel(const SolveBa
     if (d > k)
       d = solve_direction_column<PRE>(v.state[c], v.part_pq + int64_t(c) * v.n_pq, v.n_pq, v.part_rz + int64_t(c) * n_parts,
                                       v.part_rr + int64_t(c) * n_parts, n_parts, v.p + c * v.ldw, v.z + c * v.ldw, v.n,
-                                      v.history ? v.history + c * v.ldh : nullptr, k, writer);
+                                      v.history ? v.history + c * v.ldh : nullptr, k, writer, LaunchGrid{});
     if (d == SOLVE_RUNNING) any = true;
     else ended = ended > d ? ended : d;
   }
   if (writer && !any) *v.stop = ended;
+}
+
+// ---- every segment of a partition per call (hdd_operator_solve_blocks) --------------------------------------------
+// Solves A_ss x_s = b_s for the segments s of a row interval in the same three launches per iteration, whatever the
+// number of segments.  Every workgroup of a launch finds its segment and its virtual index there (BlockSegment,
+// apply_kernels.hh) and runs the single solve's body with them, on the segment's slice of the vectors, its own
+// partial sums (at the offset first[kind]) and its own SolveState: segment s ends with the bits hdd_operator_solve
+// gives on the range (row_begin, row_begin + rows) squared.
+//
+// Stop words.  state[s].done_at is segment s's, written by the first virtual workgroup of the segment in the
+// direction launch and read by the segment's other workgroups of that launch: solve_direction_column's argument
+// holds per segment.  *stop is the call's: the largest done_at once no segment iterates (SOLVE_RUNNING before).  It
+// is computed from the stored done_at alone (solve_blocks_scan), by a launch of its own before every look of the host
+// and by one more workgroup at the end of every update launch, so that the launches behind the end of the last
+// segment return without looking their segment up.  That workgroup of update launch k reads only what earlier
+// launches stored (direction launch j stores j or j + 1 <= k) and writes while the other workgroups of launch k read:
+// it leaves SOLVE_RUNNING unless every segment is done, and then the new value is <= k -- a reader of the old value
+// goes on to its segment's done_at <= k and returns, a reader of the new value returns at once: the same decision.
+
+struct SolveBlocks {
+  BlocksArgs B;                         // B.kind: BLOCKS_PARTS (the inverse-block launch's view); the others name theirs
+  SolveState* state;                    // [n_seg]
+  int32_t* stop;                        // the call's stop word
+  double *x, *p, *q, *r, *z;            // the interval's; z == r without a preconditioner
+  const double* dinv;                   // the interval's packed inverse blocks
+  double *part_pq, *part_rz, *part_rr, *part_bb, *part_bad;   // segment s at first[BLOCKS_DOT] / first[BLOCKS_PARTS]
+  double* history;                      // nullable, history[s * ldh + k]
+  int64_t ldh;
+};
+
+// segment s as the single solve's kernels see their one column
+template <int BS>
+__device__ __forceinline__ SolveVectors blocks_column(const SolveBlocks& v, int s)
+{
+  const BlockSegment& g = v.B.seg[s];
+  const int64_t o = g.row_begin - v.B.row0;
+  const int dq = g.first[BLOCKS_DOT], dp = g.first[BLOCKS_PARTS];
+  return SolveVectors{v.state + s, v.x + o, v.p + o, v.q + o, v.r + o, v.z + o, v.dinv + o / BS * solve_packed<BS>(),
+                      v.part_pq + dq, v.part_rz + dp, v.part_rr + dp, v.part_bb + dp, g.rows, g.grid[BLOCKS_DOT],
+                      v.history ? v.history + s * v.ldh : nullptr};
+}
+
+// the inverse blocks of the whole interval in one launch, on the segments' update grids; the counts of blocks that
+// are not positive definite stay with their segment (part_bad at first[BLOCKS_PARTS]).  B.kind is BLOCKS_PARTS.
+template <int NB, int NF>
+__global__ void __launch_bounds__(256) solve_dinv_tile_blocks_kernel(const ApplyArgs a, const BlocksArgs B, double* dinv, double* part_bad)
+{
+  const int s = blocks_find(B.seg, B.n_seg, BLOCKS_PARTS, blockIdx.x);
+  const BlockSegment& g = B.seg[s];
+  __shared__ double red[4];
+  solve_dinv_tile_body<NB, NF>(a, blocks_view(a, B, s), blocks_grid(g, BLOCKS_PARTS), dinv + (g.row_begin - B.row0) / NB * solve_packed<NB>(),
+                               part_bad + g.first[BLOCKS_PARTS], red);
+}
+
+template <int BS>
+__global__ void __launch_bounds__(256) solve_dinv_csr_blocks_kernel(const ApplyArgs a, const BlocksArgs B, double* dinv, double* part_bad)
+{
+  const int s = blocks_find(B.seg, B.n_seg, BLOCKS_PARTS, blockIdx.x);
+  const BlockSegment& g = B.seg[s];
+  __shared__ double red[4];
+  solve_dinv_csr_body<BS>(a, blocks_view(a, B, s), blocks_grid(g, BLOCKS_PARTS), dinv + (g.row_begin - B.row0) / BS * solve_packed<BS>(),
+                          part_bad + g.first[BLOCKS_PARTS], red);
+}
+
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_init_blocks_kernel(const SolveBlocks v, const double* b, bool x0)
+{
+  const int s = blocks_find(v.B.seg, v.B.n_seg, BLOCKS_PARTS, blockIdx.x);
+  const BlockSegment& g = v.B.seg[s];
+  __shared__ double red[3][4];
+  cg_init_body<BS, PRE, A16>(blocks_column<BS>(v, s), b + (g.row_begin - v.B.row0), x0, blocks_grid(g, BLOCKS_PARTS), red);
+}
+
+// Setup, one wave per segment: cg_init_state_kernel's sums and solve_init_column
+__global__ void __launch_bounds__(64) cg_init_state_blocks_kernel(const SolveBlocks v, bool pre, double rtol, double atol)
+{
+  const int s = blockIdx.x;
+  const BlockSegment& g = v.B.seg[s];
+  const int n_parts = g.grid[BLOCKS_PARTS], o = g.first[BLOCKS_PARTS];
+  const double bad = solve_wave_sum(v.part_bad + o, pre ? n_parts : 0);
+  const double bb = solve_wave_sum(v.part_bb + o, n_parts);
+  const double rz = solve_wave_sum(v.part_rz + o, n_parts);
+  const double rr = solve_wave_sum(v.part_rr + o, n_parts);
+  if (threadIdx.x == 0) solve_init_column(v.state[s], v.history ? v.history + s * v.ldh : nullptr, bad, bb, rz, rr, rtol, atol);
+}
+
+// *stop = the largest done_at of the segments (SOLVE_RUNNING, the largest int32_t, while one iterates), by one
+// workgroup of 256 threads
+__device__ __forceinline__ void solve_blocks_scan(const SolveState* state, int n_seg, int32_t* stop)
+{
+  __shared__ int32_t red[4];
+  int32_t m = 0;
+  for (int i = threadIdx.x; i < n_seg; i += 256) {
+    const int32_t d = state[i].done_at;
+    m = m > d ? m : d;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    const int32_t o = __shfl_xor(m, d, 64);
+    m = m > o ? m : o;
+  }
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int i = 1; i < 4; ++i) m = m > red[i] ? m : red[i];
+    *stop = m;   // other workgroups of an update launch may read the old or the new value: the same decision (above)
+  }
+}
+
+// before the first iteration and before every look of the host
+__global__ void __launch_bounds__(256) cg_stop_blocks_kernel(const SolveState* state, int n_seg, int32_t* stop)
+{
+  solve_blocks_scan(state, n_seg, stop);
+}
+
+// the launch has one workgroup more than the segments' update grids together: the last one renews the stop word
+template <int BS, bool PRE, bool A16>
+__global__ void __launch_bounds__(256) cg_update_blocks_kernel(const SolveBlocks v, int k)
+{
+  __shared__ double red[2][4];
+  if (*v.stop <= k) return;   // (uniform)
+  if (blockIdx.x == gridDim.x - 1) {
+    solve_blocks_scan(v.state, v.B.n_seg, v.stop);
+    return;
+  }
+  const int s = blocks_find(v.B.seg, v.B.n_seg, BLOCKS_PARTS, blockIdx.x);
+  const BlockSegment& g = v.B.seg[s];
+  cg_update_body<BS, PRE, A16>(blocks_column<BS>(v, s), k, blocks_grid(g, BLOCKS_PARTS), red);
+}
+
+template <bool PRE>
+__global__ void __launch_bounds__(256) cg_direction_blocks_kernel(const SolveBlocks v, int k)
+{
+  if (*v.stop <= k) return;   // (uniform)
+  const int s = blocks_find(v.B.seg, v.B.n_seg, BLOCKS_DIRECTION, blockIdx.x);
+  const BlockSegment& g = v.B.seg[s];
+  const SolveVectors c = blocks_column<1>(v, s);   // (the inverse blocks are not read here)
+  if (c.state->done_at <= k) return;   // (uniform)
+  const VirtualGrid grid = blocks_grid(g, BLOCKS_DIRECTION);
+  solve_direction_column<PRE>(*c.state, c.part_pq, c.n_pq, c.part_rz, c.part_rr, g.grid[BLOCKS_PARTS], c.p, c.z, c.n, c.history, k,
+                              grid.w() == 0 && threadIdx.x == 0, grid);
 }
 
 }  // namespace dev

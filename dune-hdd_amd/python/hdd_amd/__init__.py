@@ -103,6 +103,7 @@ class BlockRange(C.Structure):
 
 
 MAX_VEC = 8
+MAX_SOLVE_BLOCKS = 4096
 PRECOND_NONE, PRECOND_BLOCK_JACOBI = 0, 1
 SOLVE_CONVERGED, SOLVE_MAX_ITER, SOLVE_BREAKDOWN = 0, 1, 2
 SOLVE_X0 = 1
@@ -247,6 +248,10 @@ def lib():
         "hdd_operator_solve_multi_workspace": (_I64, [_I64, _I32, _I32]),
         "hdd_operator_solve_multi": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I64, _VP, _VP, _I64, _VP, _I64, _I32, _VP, _VP,
                                             _I64, _VP, _I64, _VP, _VP]),
+        "hdd_operator_apply_blocks": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP]),
+        "hdd_operator_solve_blocks_workspace": (_I64, [_I64, _I32, _I32]),
+        "hdd_operator_solve_blocks": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64,
+                                             _VP, _VP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1104,6 +1109,80 @@ def solve_multi(ctx, dpattern, vals, B, thetas, dmesh=None, block=None, X0=None,
         i.history = None if hist is None else hist[j, :i.iterations + 1]
         out.append(i)
     return X, out
+
+
+def _segment_bounds(who, dpattern, dmesh, bounds, subdomains, grid):
+    """the row bounds of the segments as a host int64 array [n_blocks + 1]: bounds as given, or one segment per
+    subdomain of subdomains=(s0, s1) of `grid` (default: the grid of the pattern's or the mesh's LocalMesh)"""
+    if (bounds is None) == (subdomains is None):
+        raise HddError("%s: give bounds= (rows) or subdomains=(s0, s1)" % who)
+    if bounds is None:
+        if grid is None:
+            local = getattr(dpattern, "local", None) or (dmesh.local if dmesh is not None else None)
+            if local is None:
+                raise HddError("%s: subdomains= needs a Grid (grid=, or a DevicePattern / DeviceMesh that has one)" % who)
+            grid = local.grid
+        s0, s1 = subdomains
+        bounds = [grid.subdomain_range(s, s + 1)[0] * grid.nb for s in range(s0, s1)] + [grid.subdomain_range(s1 - 1, s1)[1] * grid.nb]
+    bd = np.ascontiguousarray(bounds, np.int64).reshape(-1)
+    if bd.shape[0] < 2:
+        raise HddError("%s: bounds needs at least two entries" % who)
+    return bd
+
+
+def apply_blocks(ctx, dpattern, vals, x, theta=None, dmesh=None, bounds=None, subdomains=None, grid=None, out=None, stream=None):
+    """hdd_operator_apply_blocks: y_s = A_ss x_s for every segment s of a partition of a row interval in one launch --
+    apply_local_operator for all ss at once, the block-diagonal apply.  bounds: the rows [n_blocks + 1] (strictly
+    ascending), or subdomains=(s0, s1): one segment per subdomain of that range.  x: device float64
+    [bounds[-1] - bounds[0]] (unit stride), segment s at bounds[s] - bounds[0]; returns y of the same shape.  Segment s is bit for bit
+    apply(..., block=(bounds[s], bounds[s + 1], bounds[s], bounds[s + 1])) on the same path."""
+    torch = _torch()
+    vals, n, ptrs, th, _, _, _, dmesh = _apply_operands(dpattern, vals, theta, dmesh, None, grid)
+    bd = _segment_bounds("apply_blocks", dpattern, dmesh, bounds, subdomains, grid)
+    rows = int(bd[-1] - bd[0])
+    if x.dtype != torch.float64 or x.dim() != 1 or x.shape[0] != rows or (rows > 1 and x.stride(0) != 1):
+        raise HddError("apply_blocks: x must be float64 [%d] with unit stride" % rows)
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float64, device=x.device)
+    if out.dtype != torch.float64 or out.dim() != 1 or out.shape[0] != rows or (rows > 1 and out.stride(0) != 1):
+        raise HddError("apply_blocks: out must be float64 [%d] with unit stride" % rows)
+    s = stream if stream is not None else torch.cuda.current_stream(x.device).cuda_stream
+    _check(lib().hdd_operator_apply_blocks(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs, n,
+                                           _p(th), bd.shape[0] - 1, bd.ctypes.data, x.data_ptr(), out.data_ptr(), C.c_void_p(s)),
+           "hdd_operator_apply_blocks")
+    return out
+
+
+def solve_blocks(ctx, dpattern, vals, b, theta=None, dmesh=None, bounds=None, subdomains=None, grid=None, x0=None, rtol=1e-8,
+                 atol=0.0, max_iter=10000, check_every=0, precond="block_jacobi", block_size=0, history=False, stream=None):
+    """hdd_operator_solve_blocks: A_ss x_s = b_s for every segment s of a partition of a row interval in one call, three
+    launches per iteration whatever the number of segments -- the local solves of LRBMS over all subdomains, the
+    application of the non-overlapping Schwarz preconditioner.  bounds / subdomains as apply_blocks'; b (and x0): device
+    float64 [bounds[-1] - bounds[0]], segment s at bounds[s] - bounds[0]; every other argument is solve()'s and holds for
+    all segments, rtol relative to each segment's own ||b_s||.  Returns (x, infos): infos a list of SolveInfo per
+    segment (each with .history when history=True).  Segment s is bit for bit solve(..., b_s, x0=x0_s,
+    block=(bounds[s], bounds[s + 1], bounds[s], bounds[s + 1])) on the same path; EVERY A_ss MUST BE SYMMETRIC POSITIVE
+    DEFINITE."""
+    torch = _torch()
+    bd = _segment_bounds("solve_blocks", dpattern, dmesh, bounds, subdomains, grid)
+    n_blocks = int(bd.shape[0]) - 1
+    interval = BlockRange(int(bd[0]), int(bd[-1]), int(bd[0]), int(bd[-1]))
+    operator, keep, rows, _, _, x, opt, s = _solve_operands(False, dpattern, vals, theta, dmesh, interval, grid, b, x0, rtol, atol,
+                                                            max_iter, precond, block_size, check_every, stream)
+    n_work = max(int(lib().hdd_operator_solve_blocks_workspace(rows, opt.block_size, n_blocks)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
+    ldh = max(int(max_iter), 0) + 1
+    hist = torch.zeros((n_blocks, ldh), dtype=torch.float64, device=b.device) if history else None
+    infos = (SolveInfo * n_blocks)()
+    _check(lib().hdd_operator_solve_blocks(ctx.h, *operator[:5], n_blocks, bd.ctypes.data, b.data_ptr(), x.data_ptr(),
+                                           C.addressof(opt), work.data_ptr(), n_work, None if hist is None else hist.data_ptr(),
+                                           ldh, C.addressof(infos), s), "hdd_operator_solve_blocks")
+    out = []
+    for j in range(n_blocks):
+        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
+        i.history = None if hist is None else hist[j, :i.iterations + 1]
+        out.append(i)
+    return x, out
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

@@ -631,6 +631,63 @@ int hdd_operator_solve_multi(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* 
                              const hdd_solve_options* opt, double* d_work, int64_t n_work, double* d_history,
                              int64_t ldh, hdd_solve_info* info, void* stream);
 
+/* Every subdomain at once: the block-diagonal part of sum_q theta[q] A_q with respect to the segments of a partition
+ * of a row interval -- the local corrections, local Riesz representatives and enrichment solves of LRBMS, which solve
+ * on get_local_operator(ss) for ALL ss, and the non-overlapping Schwarz preconditioner sum_s R_s^T A_ss^-1 R_s.  The
+ * batch runs over row segments instead of columns.  Additive to ABI 8.
+ *
+ * bounds: host [n_blocks + 1], strictly ascending, inside the square part of the matrix; segment s is rows = columns
+ * [bounds[s], bounds[s + 1]).  The bounds are rows, not subdomain ids; a segment may be several subdomains, and the
+ * interval need neither begin at 0 nor end at n_rows.  The vectors (d_b, d_x; d_x, d_y of the apply) have bounds[n_blocks] -
+ * bounds[0] entries, segment s at bounds[s] - bounds[0].  An entry whose column lies in another segment is skipped,
+ * not multiplied by zero, as a range skips it.  The operator arguments, their checks and the dispatch are
+ * hdd_operator_apply's per segment: the tile kernel where the call on every segment's range would take it (so every
+ * bound a multiple of nb), the CSR kernel otherwise.
+ *
+ * hdd_operator_apply_blocks: y_s = A_ss x_s for every segment in one launch, one vector.  CONTRACT: segment s has the
+ * bits of hdd_operator_apply on the range (bounds[s], bounds[s + 1], bounds[s], bounds[s + 1]) on the same path.
+ * Allocates nothing (the segment table goes through buffers the context owns since its creation), no atomics, one
+ * stream at a time per context.  hdd_last_apply_kernel(): "apply_tile_blocks_kernel<3, 3>", "apply_csr_blocks_kernel<8>". */
+#define HDD_MAX_SOLVE_BLOCKS 4096
+int hdd_operator_apply_blocks(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                              int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds,
+                              const double* d_x, double* d_y, void* stream);
+/* doubles of workspace hdd_operator_solve_blocks needs: a function of (rows, block_size, n_blocks) alone, rows =
+ * bounds[n_blocks] - bounds[0] -- p, q, r, z and the packed inverse blocks of the interval, per segment a 64-byte
+ * state and a 64-byte table entry, and the partial sums of all segments together, bounded by rows / 4 + n_blocks (the
+ * workgroups of the apply) and four times rows / (256 block_size) + n_blocks (those of the update).  block_size as in
+ * hdd_operator_solve_workspace; 0 for a negative rows, a block_size outside 0..8 or n_blocks outside
+ * 1..HDD_MAX_SOLVE_BLOCKS. */
+int64_t hdd_operator_solve_blocks_workspace(int64_t rows, int32_t block_size, int32_t n_blocks);
+/* Solves A_ss x_s = b_s for every segment s in one call.  One hdd_solve_options holds for all segments (options,
+ * HDD_SOLVE_X0 -- segment s of d_x is that segment's guess --, block-Jacobi with block_size 0..8 and "no
+ * preconditioner" are hdd_operator_solve's); rtol is relative to each segment's own ||b_s||.  d_history: NULL or device
+ * [n_blocks][ldh], ldh >= max_iter + 1; info: host [n_blocks].  EVERY A_ss MUST BE SYMMETRIC POSITIVE DEFINITE
+ * (principal blocks of a definite matrix are).
+ * CONTRACT: segment s ends with exactly the x_s, iterations, residual, rhs_norm, status and history that
+ * hdd_operator_solve gives with the range (bounds[s], bounds[s + 1], bounds[s], bounds[s + 1]) on (b_s, x0_s) with the
+ * same options on the same path -- the doubles bit for bit, whatever the other segments hold and whatever check_every
+ * is.  Every segment runs on the grids its single solve has (virtual grids inside the launches), so every sum keeps
+ * its order.
+ * A segment that is done (converged, broken down, zero right-hand side) is frozen: no later launch touches its x.  A
+ * NaN, a p . Ap <= 0, a zero b_s (x_s = 0, converged, 0 iterations; only that segment of x is cleared) and a diagonal
+ * block that is not positive definite (breakdown before the first iteration: the count is kept per segment) stay
+ * with their own segment.  Returns HDD_OK for every mix of statuses.
+ * One iteration of the whole call is three launches, whatever n_blocks is; every launch reads the call's stop word
+ * (the iteration at which the last live segment ended), then its segment's.  A look of the host renews and reads the
+ * call's stop word and SYNCHRONISES `stream`; the per-segment states are read once, at the end.  Allocates nothing, no
+ * atomics, one stream at a time per context; the segment table is one copy into the workspace per call.
+ * HDD_ERR_INVALID (every argument check precedes the first device call) for what hdd_operator_solve rejects, n_blocks
+ * outside 1..HDD_MAX_SOLVE_BLOCKS, null bounds, bounds not strictly ascending or outside the matrix, a bound that is no
+ * multiple of the resolved block size, ldh < max_iter + 1 with a history, n_work below
+ * hdd_operator_solve_blocks_workspace, a null info.
+ * hdd_last_solve_kernels(): "apply_tile_blocks_kernel<3, 3, dot> + cg_update_blocks<3> + cg_direction_blocks"
+ * ("apply_csr_blocks_kernel<8, dot>" on the CSR path, "cg_update_blocks<3, none>" without a preconditioner). */
+int hdd_operator_solve_blocks(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                              int32_t n_comp, const double* theta, int32_t n_blocks, const int64_t* bounds,
+                              const double* d_b, double* d_x, const hdd_solve_options* opt, double* d_work,
+                              int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */
 /* GPU owns a contiguous range of subdomains and assembles their rows -- A_ss and A_ss,nn are written  */

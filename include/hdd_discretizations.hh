@@ -850,6 +850,78 @@ class AffinelyDecomposedMatrix {
     for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
     return x;
   }
+  // x_s = A_ss(mu)^-1 b_s for every segment s of a partition of a row interval in one device solve
+  // (hdd_operator_solve_blocks): bounds [n + 1] are rows, strictly ascending; d_b, d_x: device [bounds[n] - bounds[0]],
+  // segment s at bounds[s] - bounds[0].  Three launches per iteration whatever n is; segment s is bit for bit what
+  // apply_inverse gives on the range (bounds[s], bounds[s + 1]) squared.  Every A_ss(mu) must be symmetric positive
+  // definite.  Throws linear_solver_failed naming the first segment that did not converge.
+  std::vector<hdd_solve_info> apply_inverse_blocks(const std::vector<int64_t>& bounds, const double* d_b, double* d_x, double mu = 0.0,
+                                                   const SolverOptions& options = SolverOptions(), bool x0 = false,
+                                                   void* stream = nullptr) const
+  {
+    if (bounds.size() < 2 || bounds.size() > size_t(HDD_MAX_SOLVE_BLOCKS) + 1)
+      throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
+    const int32_t n = int32_t(bounds.size()) - 1;
+    std::vector<const double*> v;
+    std::vector<double> theta;
+    operands(mu, v, theta);
+    const hdd_csr pat = pattern->csr();
+    const int64_t rows = bounds.back() - bounds.front();
+    const hdd_solve_options opt = solve_options(options, x0);
+    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_blocks_workspace(std::max<int64_t>(rows, 0), opt.block_size, n), 1);
+    internal::DeviceArray<double> work{size_t(n_work)};
+    std::vector<hdd_solve_info> infos(size_t(n), hdd_solve_info{});
+    internal::check(hdd_operator_solve_blocks(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()), theta.data(),
+                                              n, bounds.data(), d_b, d_x, &opt, work.get(), n_work, nullptr, 0, infos.data(), stream),
+                    "hdd_operator_solve_blocks");
+    for (int32_t j = 0; j < n; ++j)
+      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
+        throw Stuff::Exceptions::linear_solver_failed(solver_failed(
+            infos[size_t(j)], " for segment " + std::to_string(j) + " of " + std::to_string(n) + " (rows " +
+                                  std::to_string(bounds[size_t(j)]) + " .. " + std::to_string(bounds[size_t(j) + 1]) + ")"));
+    return infos;
+  }
+  std::vector<double> apply_inverse_blocks(const std::vector<int64_t>& bounds, const std::vector<double>& b, double mu = 0.0,
+                                           const SolverOptions& options = SolverOptions(),
+                                           std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    if (bounds.size() < 2) throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
+    const int64_t rows = bounds.back() - bounds.front();
+    if (int64_t(b.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: b has the wrong size");
+    internal::DeviceArray<double> db{size_t(std::max<int64_t>(rows, 1))}, dx{size_t(std::max<int64_t>(rows, 1))};
+    if (rows) internal::hip_check(hipMemcpy(db.get(), b.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_inverse_blocks");
+    const auto i = apply_inverse_blocks(bounds, db.get(), dx.get(), mu, options);
+    if (infos) *infos = i;
+    auto x = dx.download();
+    x.resize(size_t(rows));
+    return x;
+  }
+  // y_s = A_ss(mu) x_s for every segment in one launch (hdd_operator_apply_blocks); asynchronous on `stream`
+  void apply_blocks(const std::vector<int64_t>& bounds, const double* d_x, double* d_y, double mu = 0.0, void* stream = nullptr) const
+  {
+    if (bounds.size() < 2 || bounds.size() > size_t(HDD_MAX_SOLVE_BLOCKS) + 1)
+      throw Stuff::Exceptions::wrong_input_given("apply_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
+    std::vector<const double*> v;
+    std::vector<double> theta;
+    operands(mu, v, theta);
+    const hdd_csr pat = pattern->csr();
+    internal::check(hdd_operator_apply_blocks(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()), theta.data(),
+                                              int32_t(bounds.size()) - 1, bounds.data(), d_x, d_y, stream),
+                    "hdd_operator_apply_blocks");
+  }
+  std::vector<double> apply_blocks(const std::vector<int64_t>& bounds, const std::vector<double>& x, double mu = 0.0) const
+  {
+    if (bounds.size() < 2) throw Stuff::Exceptions::wrong_input_given("apply_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
+    const int64_t rows = bounds.back() - bounds.front();
+    if (int64_t(x.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_blocks: x has the wrong size");
+    internal::DeviceArray<double> dx{size_t(std::max<int64_t>(rows, 1))}, dy{size_t(std::max<int64_t>(rows, 1))};
+    if (rows) internal::hip_check(hipMemcpy(dx.get(), x.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_blocks");
+    apply_blocks(bounds, dx.get(), dy.get(), mu);
+    internal::hip_check(hipDeviceSynchronize(), "apply_blocks");
+    auto y = dy.download();
+    y.resize(size_t(rows));
+    return y;
+  }
   // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
   // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
   void set_tile_mesh(const hdd_mesh& m, std::shared_ptr<internal::DeviceArray<int32_t>> nbrs)
@@ -1733,6 +1805,34 @@ class BlockSWIPDG : public SWIPDG {
     const int64_t nb = info_.nb;
     const hdd_block_range rng{a * nb, e * nb, a * nb, e * nb};
     return system_matrix().apply_inverse(b, mus, options, &rng, infos);
+  }
+
+  // The rows at which the subdomains begin, and the end of the last: the segments of solve_locals /
+  // apply_local_operators
+  std::vector<int64_t> subdomain_bounds() const
+  {
+    std::vector<int64_t> bounds;
+    int64_t a = 0, e = 0;
+    for (int ss = 0; ss < num_subdomains(); ++ss) {
+      internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &e), "range");
+      bounds.push_back(a * info_.nb);
+    }
+    bounds.push_back(e * info_.nb);
+    return bounds;
+  }
+  // solve_local(ss, b_ss) for ALL subdomains in one device solve (hdd_operator_solve_blocks): b holds the local
+  // right-hand sides one behind the other (the global numbering), and so does the result.  Subdomain ss is bit for bit
+  // what solve_local(ss, ...) gives.  Throws linear_solver_failed naming the first subdomain that did not converge.
+  std::vector<double> solve_locals(const std::vector<double>& b, double mu = 0.0,
+                                   const AffinelyDecomposedMatrix::SolverOptions& options = AffinelyDecomposedMatrix::SolverOptions(),
+                                   std::vector<hdd_solve_info>* infos = nullptr) const
+  {
+    return system_matrix().apply_inverse_blocks(subdomain_bounds(), b, mu, options, infos);
+  }
+  // apply_local_operator(ss, x_ss) for all subdomains in one launch: the block-diagonal part of A(mu)
+  std::vector<double> apply_local_operators(const std::vector<double>& x, double mu = 0.0) const
+  {
+    return system_matrix().apply_blocks(subdomain_bounds(), x, mu);
   }
 
   // block-swipdg.hh:678-685: the local vector of ss (local discretization rhs + boundary contributions) =

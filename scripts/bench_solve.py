@@ -22,8 +22,14 @@ as above; model per iteration 8 nnz n_comp + (BS + 1) / 2 8 n per group of four 
 against N hdd_operator_solve calls at those thetas: theta_j = (1, mu_j), mu_j spread over [0.3, 1], on the two
 components of c3 (definite from mu = 0.3 up once it is at 0.3), a scalar theta_j in [1, 2] on the one component of c2 /
 c4; model per iteration 8 nnz n_comp per group of four columns + (13 + (BS + 1) / 2) 8 n per column.
+--blocks PX,PY measures, by the same protocol, one hdd_operator_solve_blocks call over all PX x PY subdomains of the
+configuration's mesh against the loop of hdd_operator_solve with block=(ss, ss) over the same subdomains (one
+subdomain per call: the path before), every segment checked for bit equality with its single solve in every round;
+for comparison the record carries the model of the single whole-matrix iteration (the tile kernel streams the
+coupling blocks of a row block, too, and skips them) and its rate at both times.
 Prints one JSON line per configuration; --out DIR also writes them to DIR/bench_solve.jsonl (--rhs:
-DIR/bench_solve_batched.jsonl, --thetas: DIR/bench_solve_multi.jsonl)."""
+DIR/bench_solve_batched.jsonl, --thetas: DIR/bench_solve_multi.jsonl, --blocks: appended to
+DIR/bench_solve_blocks.jsonl, one run per partition)."""
 import argparse
 import json
 import math
@@ -53,14 +59,15 @@ def inverse_blocks(torch, loc, dm, dp, vals, theta):
     return torch.linalg.inv(D)
 
 
-def build(name, n):
-    """the meshes and coefficients of scripts/bench_apply.py's configurations; returns an assemble(sigma_scale)"""
+def build(name, n, part=(1, 1)):
+    """the meshes and coefficients of scripts/bench_apply.py's configurations (part: subdomains in x and y); returns an
+    assemble(sigma_scale)"""
     import torch
     import hdd_amd as H
     ctx = H.Context(0)
     if name == "c3":
         n = n or 1024
-        grid = H.Grid.structured(H.SIMPLEX, n, n, (-1, -1), (1, 1))
+        grid = H.Grid.structured(H.SIMPLEX, n, n, (-1, -1), (1, 1), px=part[0], py=part[1])
         kx, ky = 4 * math.pi, 2 * math.pi
         fns = [H.scalar_fn(H.FN_SINUSOID, 1.0, 0.75, kx, ky, order=3),
                H.scalar_fn(H.FN_SINUSOID, 0.0, -0.75, kx, ky, order=3)]
@@ -71,7 +78,7 @@ def build(name, n):
         et = H.SIMPLEX if name == "c2" else H.CUBE
         nx = n or (3200 if name == "c2" else 3520)
         ny = nx // 5 if name == "c2" else nx * 1200 // 3520
-        grid = H.Grid.structured(et, nx, ny, (0, 0), (5, 1))
+        grid = H.Grid.structured(et, nx, ny, (0, 0), (5, 1), px=part[0], py=part[1])
         loc = grid.local()
         k = loc.checkerboard((0, 0), (5, 1), 100, 20, 10.0 ** np.random.default_rng(10).uniform(-3, 3, 2000))
         fns = [H.scalar_fn(H.FN_CONST, 1.0)]
@@ -155,10 +162,71 @@ def run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, 
     print(json.dumps(res), flush=True)
 
 
+def run_blocks(args, torch, H, ctx, loc, dm, dp, vals, theta, label, reference, scale, gen):
+    """--blocks PX,PY: one hdd_operator_solve_blocks call over all subdomains against the loop of single solves with
+    block=(ss, ss), alternating over the rounds in this process"""
+    grid, nb = loc.grid, loc.nb
+    n, nnz, nc, iters = dp.t.n_rows, dp.nnz, len(vals), args.iters
+    S = args.blocks[0] * args.blocks[1]
+    bounds = [grid.subdomain_range(s, s + 1)[0] * nb for s in range(S)] + [grid.subdomain_range(S - 1, S)[1] * nb]
+    assert bounds[0] == 0 and bounds[-1] == n
+    b = torch.randn(n, dtype=torch.float64, device="cuda", generator=gen)
+
+    def blocks(k):
+        return H.solve_blocks(ctx, dp, vals, b, theta=theta, dmesh=dm, bounds=bounds, rtol=0.0, max_iter=k, check_every=max(k, 1))
+
+    def singles(k):
+        return [H.solve(ctx, dp, vals, b[bounds[s]:bounds[s + 1]], theta=theta, dmesh=dm, block=(s, s), grid=grid, rtol=0.0,
+                        max_iter=k, check_every=max(k, 1)) for s in range(S)]
+
+    def timed(fn, k):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn(k)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1), out
+
+    timed(blocks, 3), timed(singles, 3)   # warm-up
+    names = {}
+    ms = dict(blocks=[], blocks_setup=[], singles=[], singles_setup=[])
+    per = dict(blocks=[], singles=[])
+    identical = True
+    for _ in range(args.rounds):
+        t, (x, infos) = timed(blocks, iters)
+        names["blocks"] = H.last_solve_kernels()
+        ms["blocks"].append(t)
+        ms["blocks_setup"].append(timed(blocks, 0)[0])
+        t, one = timed(singles, iters)
+        names["singles"] = H.last_solve_kernels()
+        ms["singles"].append(t)
+        ms["singles_setup"].append(timed(singles, 0)[0])
+        for k in per:
+            per[k].append((ms[k][-1] - ms[k + "_setup"][-1]) / iters)
+        for s in range(S):
+            xs, i = one[s]
+            identical = identical and bool(torch.equal(x[bounds[s]:bounds[s + 1]].view(torch.int64), xs.view(torch.int64))) and \
+                (i.status, i.iterations, i.residual, i.rhs_norm) == (infos[s].status, infos[s].iterations, infos[s].residual, infos[s].rhs_norm)
+    med = {k: float(np.median(v)) for k, v in per.items()}
+    model = 8 * nnz * nc + (13 + (nb + 1) / 2) * 8 * n
+    statuses = sorted(set(i.status for i in infos))
+    res = dict(config=label, n_rows=n, nnz=nnz, n_comp=nc, block_size=nb, partition=list(args.blocks), n_blocks=S,
+               rows_per_block=dict(min=min(e - a for a, e in zip(bounds[:-1], bounds[1:])), max=max(e - a for a, e in zip(bounds[:-1], bounds[1:]))),
+               iters=iters, rounds=args.rounds, mode="blocks", reference_penalties=reference, sigma_scale=scale, kernels=names,
+               statuses=statuses, iterations=dict(min=min(i.iterations for i in infos), max=max(i.iterations for i in infos)),
+               segments_bit_identical_to_singles=identical,
+               ms={k: dict(median=float(np.median(v)), min=float(min(v)), max=float(max(v))) for k, v in ms.items()},
+               ms_per_iteration={k: dict(median=med[k], min=float(min(v)), max=float(max(v))) for k, v in per.items()},
+               blocks_over_singles=med["blocks"] / med["singles"],
+               model_bytes_per_whole_matrix_iteration=model,
+               model_GBps=dict(blocks=model / med["blocks"] / 1e6, singles=model / med["singles"] / 1e6))
+    print(json.dumps(res), flush=True)
+
+
 def run_config(args):
     import torch
     torch.cuda.set_device(0)
-    H, ctx, loc, dm, dp, assemble, label = build(args.config, args.n)
+    H, ctx, loc, dm, dp, assemble, label = build(args.config, args.n, args.blocks or (1, 1))
     vals = assemble(1.0)
     n, nnz, nb, nc = dp.t.n_rows, dp.nnz, loc.nb, len(vals)
     theta = [1.0, 0.3][:nc]
@@ -172,6 +240,8 @@ def run_config(args):
         scale *= args.sigma_scale
         vals = assemble(scale, vals)
         _, i0 = H.solve(ctx, dp, vals, b, theta=theta, dmesh=dm, rtol=0.0, max_iter=iters, check_every=iters)
+    if args.blocks:
+        return run_blocks(args, torch, H, ctx, loc, dm, dp, vals, theta, label, reference, scale, gen)
     if args.rhs or args.thetas:
         return run_batched(args, torch, H, ctx, nb, dm, dp, vals, theta, label, reference, scale, gen)
     Dinv = inverse_blocks(torch, loc, dm, dp, vals, theta)
@@ -248,6 +318,9 @@ def main():
                     "solves instead (bench_solve_batched.jsonl)")
     ap.add_argument("--thetas", type=int, default=0, help="N > 0: time one solve_multi of N columns at N thetas against N single "
                     "solves at those thetas instead (bench_solve_multi.jsonl)")
+    ap.add_argument("--blocks", type=lambda v: tuple(int(t) for t in v.split(",")), default=None,
+                    help="PX,PY: time one solve_blocks over all PX x PY subdomains against the loop of single local solves instead "
+                    "(appended to bench_solve_blocks.jsonl)")
     ap.add_argument("--timeout", type=float, default=240.0, help="seconds per configuration (child process)")
     ap.add_argument("--out", default=None, help="directory for bench_solve.jsonl")
     args = ap.parse_args()
@@ -259,6 +332,8 @@ def main():
         cmd = [sys.executable, os.path.abspath(__file__), "--config", c, "--n", str(args.n), "--iters", str(args.iters),
                "--rounds", str(args.rounds), "--converge", str(args.converge), "--sigma-scale", str(args.sigma_scale), "--rhs", str(args.rhs),
                "--thetas", str(args.thetas)]
+        if args.blocks:
+            cmd += ["--blocks", "%d,%d" % args.blocks]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=args.timeout)
         except subprocess.TimeoutExpired:
@@ -273,7 +348,8 @@ def main():
                 print(ln, flush=True)
     if args.out:
         os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, "bench_solve_multi.jsonl" if args.thetas else "bench_solve_batched.jsonl" if args.rhs else "bench_solve.jsonl"), "w") as f:
+        name = "bench_solve_blocks.jsonl" if args.blocks else "bench_solve_multi.jsonl" if args.thetas else "bench_solve_batched.jsonl" if args.rhs else "bench_solve.jsonl"
+        with open(os.path.join(args.out, name), "a" if args.blocks else "w") as f:
             f.write("\n".join(lines) + "\n")
     return 0
 
