@@ -627,6 +627,8 @@ extern "C" int hdd_local_create(const hdd_grid* g, int32_t s_begin, int32_t s_en
 
 extern "C" void hdd_local_destroy(hdd_local* l) { delete l; }
 
+int hdd::local_elem_type(const hdd_local* l) { return l->impl.g->elem_type; }
+
 extern "C" int hdd_local_get_info(const hdd_local* l, hdd_local_info* out)
 {
   if (!l || !out) return set_error(HDD_ERR_INVALID, "hdd_local_get_info: null argument");

@@ -2,7 +2,9 @@
 // The reference reports failures with DUNE_THROW (swipdg.hh:173-176, base.hh:285-289); across the C ABI
 // they become status codes plus a per-thread message (hdd_last_error).
 #pragma once
+#include <cstdint>
 #include <string>
+#include <vector>
 
 #include "hdd.h"
 
@@ -13,6 +15,19 @@ std::string& last_error_slot();
 const char*& last_tile_kernel_slot();
 int set_error(int code, const std::string& msg);
 int ctx_device(const hdd_ctx* ctx);   // HIP device ordinal a context is bound to
+int local_elem_type(const hdd_local* l);   // HDD_SIMPLEX | HDD_CUBE | HDD_HEX of the grid behind a local view
+
+// Host tables of the ESV2007 estimator (hdd_estimator_create; estimator_tables.cpp), from the host view alone: the
+// vertex -> DoF CSR (DoF 3 e + i of every element e with local vertex i at the vertex, ascending) and the flags of the
+// vertices on a boundary face, in the vertex numbering of hdd_local_vertices.  Rejects what the estimator does not
+// cover (HDD_ERR_UNSUPPORTED: no 2d simplex grid, a view with ghosts, a Neumann face, 3 n_local >= 2^31).
+struct EstimatorTables {
+  int64_t n_local = 0, n_vertices = 0;
+  std::vector<int64_t> patch_ptr;
+  std::vector<int32_t> patch_dof;
+  std::vector<uint8_t> vertex_bnd;
+};
+int estimator_tables(const hdd_local* l, EstimatorTables* out);
 }  // namespace hdd
 
 // Sharded-step fixup off the assembly stream (abi_assemble.hip, used by shard_step.hip): the element-list pass into side

@@ -1,0 +1,301 @@
+// dune-hdd_amd/csrc/kernels/estimate.hip -- kernels of the ESV2007 estimator (estimate_kernels.hh has the launch
+// structure and the order of every sum; hdd.h hdd_swipdg_estimate the definitions).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "elem_affine.hh"
+#include "estimate_kernels.hh"
+
+namespace hdd {
+namespace dev {
+namespace {
+
+// Oswald interpolation: lane v owns vertex v.  The mean is taken about the first value, first + sum(u_k - first) / m,
+// in ascending DoF order: a vector that is already continuous comes back bit for bit.
+__global__ void __launch_bounds__(ESTIMATE_WG)
+oswald_vertex_kernel(int64_t n_vertices, const int64_t* __restrict__ patch_ptr, const int32_t* __restrict__ patch_dof,
+                     const uint8_t* __restrict__ vertex_bnd, const double* __restrict__ u, double* __restrict__ oswald,
+                     double* __restrict__ out)
+{
+  const int64_t v = int64_t(blockIdx.x) * ESTIMATE_WG + threadIdx.x;
+  if (v >= n_vertices) return;
+  const int64_t b = patch_ptr[v], e = patch_ptr[v + 1];
+  double m = 0.0;
+  if (!vertex_bnd[v] && e > b) {
+    const double first = u[patch_dof[b]];
+    double s = 0.0;
+    for (int64_t k = b + 1; k < e; ++k) s += u[patch_dof[k]] - first;
+    m = first + s / double(e - b);
+  }
+  oswald[v] = m;
+  if (out) out[v] = m;
+}
+
+// vertices, coordinates and DoFs of element e
+__device__ __forceinline__ void load_element(const EstimateArgs& a, int64_t e, int32_t v[3], double p[3][2], double w[3])
+{
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    v[i] = a.ev[i * a.n + e];
+    p[i][0] = a.vxy[2 * int64_t(v[i])];
+    p[i][1] = a.vxy[2 * int64_t(v[i]) + 1];
+    w[i] = a.u[3 * e + i];
+  }
+}
+
+__device__ __forceinline__ double tri_det(const double p[3][2])
+{
+  return (p[1][0] - p[0][0]) * (p[2][1] - p[0][1]) - (p[2][0] - p[0][0]) * (p[1][1] - p[0][1]);
+}
+
+// gradient of the P1 function with the vertex values w
+__device__ __forceinline__ void p1_gradient(const double p[3][2], double det, const double w[3], double g[2])
+{
+  g[0] = (w[0] * (p[1][1] - p[2][1]) + w[1] * (p[2][1] - p[0][1]) + w[2] * (p[0][1] - p[1][1])) / det;
+  g[1] = (w[0] * (p[2][0] - p[1][0]) + w[1] * (p[0][0] - p[2][0]) + w[2] * (p[1][0] - p[0][0])) / det;
+}
+
+// symmetric tensor A_T as (a11, a12, a22)
+__device__ __forceinline__ void tensor_of(const EstimateArgs& a, int64_t e, double A[3])
+{
+  double M[3][3];
+  elem_tensor(a.tkind, a.tc, a.tper, a.n, e, 2, M);
+  A[0] = M[0][0];
+  A[1] = M[0][1];
+  A[2] = M[1][1];
+}
+
+// kappa_T(theta) = sum_q theta_q kappa_q,T for the NR first parameter roles
+template <int NR>
+__device__ __forceinline__ void kappa_of(const EstimateArgs& a, int64_t e, double k[NR])
+{
+#pragma unroll
+  for (int r = 0; r < NR; ++r) k[r] = 0.0;
+  for (int q = 0; q < a.n_comp; ++q) {
+    const double kq = a.kper[q] ? a.kper[q][e] : a.kconst[q];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) k[r] += a.theta[r][q] * kq;
+  }
+}
+
+__device__ __forceinline__ double quad_form(const double K[3], double x0, double x1, double y0, double y1)
+{
+  return K[0] * x0 * y0 + K[1] * (x0 * y1 + x1 * y0) + K[2] * x1 * y1;
+}
+
+template <int FORCE>
+__device__ __forceinline__ double force_at(const EstimateArgs& a, int64_t e, const double* x)
+{
+  if constexpr (FORCE == 1) return a.force.c * cos_phase(a.force.kx * x[0]) * cos_phase(a.force.ky * x[1]);
+  else return fn_value(a.force, e, x, 2);
+}
+
+// h_T^2 / (pi^2 lambda_min(K)) int_T (f - P0 f)^2; with residual_star div t_h (constant on T) stands for P0 f
+template <int FORCE>
+__device__ __forceinline__ double residual2(const EstimateArgs& a, int64_t e, const double p[3][2], double det,
+                                            const double K[3], double div)
+{
+  const double j00 = p[1][0] - p[0][0], j01 = p[2][0] - p[0][0], j10 = p[1][1] - p[0][1], j11 = p[2][1] - p[0][1];
+  double mean = div;
+  if (!a.residual_star) {
+    mean = 0.0;
+    for (int k = 0; k < a.nqa; ++k) {
+      const double x[2] = {p[0][0] + j00 * a.q[k][0] + j01 * a.q[k][1], p[0][1] + j10 * a.q[k][0] + j11 * a.q[k][1]};
+      mean += a.q[k][2] * force_at<FORCE>(a, e, x);
+    }
+    mean *= 2.0;
+  }
+  double s = 0.0;
+  for (int k = a.nqa; k < a.nqa + a.nqb; ++k) {
+    const double x[2] = {p[0][0] + j00 * a.q[k][0] + j01 * a.q[k][1], p[0][1] + j10 * a.q[k][0] + j11 * a.q[k][1]};
+    const double d = force_at<FORCE>(a, e, x) - mean;
+    s += a.q[k][2] * (d * d);
+  }
+  double h2 = 0.0;
+#pragma unroll
+  for (int f = 0; f < 3; ++f) {
+    const int i = f == 2 ? 1 : 0, j = f == 0 ? 1 : 2;
+    const double tx = p[j][0] - p[i][0], ty = p[j][1] - p[i][1];
+    h2 = fmax(h2, tx * tx + ty * ty);
+  }
+  const double hd = 0.5 * (K[0] - K[2]);
+  const double lam = 0.5 * (K[0] + K[2]) - sqrt(hd * hd + K[1] * K[1]);
+  return h2 / (9.8696044010893586188 * lam) * (fabs(det) * s);
+}
+
+// outward flux F_T,e of the RT0 reconstruction through face F of element e (hdd.h).  A boundary face runs the same
+// arithmetic on the element's own data in place of a neighbour's (weights 1/2 exactly, so the consistency term is
+// -|e| K grad u . n) with the boundary penalty: its branch is the loads alone.
+template <int F, bool BETA1>
+__device__ __forceinline__ double face_flux(const EstimateArgs& a, int64_t e, uint32_t finfo, const double p[3][2],
+                                            const double w[3], const double K[3], const double Kg[2])
+{
+  constexpr int ia = F == 2 ? 1 : 0, ib = F == 0 ? 1 : 2, io = 2 - F;
+  const double tx = p[ib][0] - p[ia][0], ty = p[ib][1] - p[ia][1];
+  const double le = sqrt(tx * tx + ty * ty);
+  double nx = ty / le, ny = -tx / le;
+  if ((p[ia][0] - p[io][0]) * nx + (p[ia][1] - p[io][1]) * ny < 0.0) {
+    nx = -nx;
+    ny = -ny;
+  }
+  const double dm = quad_form(K, nx, ny, nx, ny);
+  const double mean_m = 0.5 * (w[ia] + w[ib]);
+  const int32_t nb = a.nbrs[F * a.n + e];
+  double dp = dm, Kgp0 = Kg[0], Kgp1 = Kg[1], mean_p = 0.0;
+  if (nb >= 0) {
+    int32_t vn[3];
+    double pn[3][2], wn[3], An[3], kn[1], gn[2];
+    load_element(a, nb, vn, pn, wn);
+    tensor_of(a, nb, An);
+    kappa_of<1>(a, nb, kn);
+    const double Kn[3] = {kn[0] * An[0], kn[0] * An[1], kn[0] * An[2]};
+    p1_gradient(pn, tri_det(pn), wn, gn);
+    Kgp0 = Kn[0] * gn[0] + Kn[1] * gn[1];
+    Kgp1 = Kn[1] * gn[0] + Kn[2] * gn[1];
+    dp = quad_form(Kn, nx, ny, nx, ny);
+    // the neighbour's trace on the edge: its DoFs on its twin face
+    const uint32_t ft = (finfo >> (4 * F)) & 7u;
+    mean_p = 0.5 * ((ft == 2 ? wn[1] : wn[0]) + (ft == 0 ? wn[1] : wn[2]));
+  }
+  const double wm = dp / (dp + dm), wp = dm / (dp + dm);
+  const double sg = nb >= 0 ? a.sigma_inner * (dp * dm / (dp + dm)) : a.sigma_boundary * dm;
+  const double pen = BETA1 ? sg : sg * (le / pow(le, a.beta));   // sigma gamma / |e|^beta * |e|
+  return -le * ((wm * Kg[0] + wp * Kgp0) * nx + (wm * Kg[1] + wp * Kgp1) * ny) + pen * (mean_m - mean_p);
+}
+
+// v[t] += v[t + s], s = ESTIMATE_WG / 2 .. 1, on the four rows of sh; the sums end in sh[k][0]
+__device__ __forceinline__ void tree_sum(double (*sh)[ESTIMATE_WG], int t)
+{
+  for (int s = ESTIMATE_WG / 2; s >= 1; s >>= 1) {
+    __syncthreads();
+    if (t < s) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sh[k][t] += sh[k][t + s];
+    }
+  }
+  __syncthreads();
+}
+
+// FORCE: 0 no residual term, 1 HDD_FN_COS_PRODUCT inline, 2 any kind through fn_value
+template <bool BETA1, int FORCE>
+__global__ void __launch_bounds__(ESTIMATE_WG) esv2007_element_kernel(const EstimateArgs a)
+{
+  __shared__ double sh[4][ESTIMATE_WG];
+  const int t = threadIdx.x;
+  const int64_t e = int64_t(blockIdx.x) * ESTIMATE_WG + t;
+  double eta[4] = {0.0, 0.0, 0.0, 0.0};
+  if (e < a.n) {
+    int32_t v[3];
+    double p[3][2], w[3], A[3], k[3];
+    load_element(a, e, v, p, w);
+    tensor_of(a, e, A);
+    kappa_of<3>(a, e, k);
+    const double det = tri_det(p), area = 0.5 * fabs(det);
+    const double Kmu[3] = {k[0] * A[0], k[0] * A[1], k[0] * A[2]};
+    double g[2];
+    p1_gradient(p, det, w, g);
+    {   // nonconformity: |T| grad(u - I_OS u)^T K(theta_bar) grad(u - I_OS u)
+      const double Kbar[3] = {k[1] * A[0], k[1] * A[1], k[1] * A[2]};
+      const double d[3] = {w[0] - a.oswald[v[0]], w[1] - a.oswald[v[1]], w[2] - a.oswald[v[2]]};
+      double gd[2];
+      p1_gradient(p, det, d, gd);
+      eta[0] = area * quad_form(Kbar, gd[0], gd[1], gd[0], gd[1]);
+    }
+    // diffusive flux reconstruction
+    const double Kg[2] = {Kmu[0] * g[0] + Kmu[1] * g[1], Kmu[1] * g[0] + Kmu[2] * g[1]};
+    const uint32_t finfo = a.finfo[e];
+    const double F[3] = {face_flux<0, BETA1>(a, e, finfo, p, w, Kmu, Kg), face_flux<1, BETA1>(a, e, finfo, p, w, Kmu, Kg),
+                         face_flux<2, BETA1>(a, e, finfo, p, w, Kmu, Kg)};
+    {   // (grad u + Khat^-1 t_h)^T Khat (grad u + Khat^-1 t_h) at the three edge midpoints
+      const double Khat[3] = {k[2] * A[0], k[2] * A[1], k[2] * A[2]};
+      const double dK = Khat[0] * Khat[2] - Khat[1] * Khat[1];
+      const double Ki[3] = {Khat[2] / dK, -Khat[1] / dK, Khat[0] / dK};
+      const double c[3] = {F[0] / (2.0 * area), F[1] / (2.0 * area), F[2] / (2.0 * area)};
+      double s = 0.0;
+#pragma unroll
+      for (int f = 0; f < 3; ++f) {
+        const int i = f == 2 ? 1 : 0, j = f == 0 ? 1 : 2;
+        const double mx = 0.5 * (p[i][0] + p[j][0]), my = 0.5 * (p[i][1] + p[j][1]);
+        const double tx = c[0] * (mx - p[2][0]) + c[1] * (mx - p[1][0]) + c[2] * (mx - p[0][0]);
+        const double ty = c[0] * (my - p[2][1]) + c[1] * (my - p[1][1]) + c[2] * (my - p[0][1]);
+        const double w0 = g[0] + (Ki[0] * tx + Ki[1] * ty), w1 = g[1] + (Ki[1] * tx + Ki[2] * ty);
+        s += (area / 3.0) * quad_form(Khat, w0, w1, w0, w1);
+      }
+      eta[2] = s;
+    }
+    if (FORCE != 0) eta[1] = residual2<FORCE>(a, e, p, det, Kmu, (F[0] + F[1] + F[2]) / area);
+    const double rd = sqrt(fmax(eta[1], 0.0)) + sqrt(fmax(eta[2], 0.0));
+    eta[3] = eta[0] + rd * rd;
+    if (a.out_local) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) a.out_local[r * a.n + e] = eta[r];
+    }
+    if (a.out_flux) {
+#pragma unroll
+      for (int f = 0; f < 3; ++f) a.out_flux[f * a.n + e] = F[f];
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) sh[r][t] = eta[r];
+  tree_sum(sh, t);
+  if (t < 4) a.partial[int64_t(t) * gridDim.x + blockIdx.x] = sh[t][0];
+}
+
+__global__ void __launch_bounds__(ESTIMATE_WG) estimate_sum_kernel(const double* __restrict__ partial, int64_t n_wg,
+                                                                    double* __restrict__ total)
+{
+  __shared__ double sh[4][ESTIMATE_WG];
+  const int t = threadIdx.x;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    double s = 0.0;
+    for (int64_t k = t; k < n_wg; k += ESTIMATE_WG) s += partial[r * n_wg + k];
+    sh[r][t] = s;
+  }
+  tree_sum(sh, t);
+  if (t < 4) total[t] = sh[t][0];
+}
+
+template <bool BETA1, int FORCE>
+hipError_t launch_element(const EstimateArgs& a, unsigned n_wg, hipStream_t s)
+{
+  hipLaunchKernelGGL((esv2007_element_kernel<BETA1, FORCE>), dim3(n_wg), dim3(ESTIMATE_WG), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t launch_estimate(const EstimateArgs& a, hipStream_t s, const char** names)
+{
+  const int64_t n_wg = estimate_workgroups(a.n), v_wg = (a.n_vertices + ESTIMATE_WG - 1) / ESTIMATE_WG;
+  if (v_wg > 0) {
+    hipLaunchKernelGGL(oswald_vertex_kernel, dim3(unsigned(v_wg)), dim3(ESTIMATE_WG), 0, s, a.n_vertices, a.patch_ptr,
+                       a.patch_dof, a.vertex_bnd, a.u, a.oswald, a.out_oswald);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
+  hipError_t e;
+  if (a.beta_is_one) {
+    static const char* nm[3] = {"oswald_vertex_kernel + esv2007_element_kernel<beta1, no_force>",
+                                "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>",
+                                "oswald_vertex_kernel + esv2007_element_kernel<beta1, generic_force>"};
+    *names = nm[force];
+    e = force == 0 ? launch_element<true, 0>(a, unsigned(n_wg), s)
+                   : (force == 1 ? launch_element<true, 1>(a, unsigned(n_wg), s) : launch_element<true, 2>(a, unsigned(n_wg), s));
+  } else {
+    static const char* nm[3] = {"oswald_vertex_kernel + esv2007_element_kernel<pow, no_force>",
+                                "oswald_vertex_kernel + esv2007_element_kernel<pow, cos_product>",
+                                "oswald_vertex_kernel + esv2007_element_kernel<pow, generic_force>"};
+    *names = nm[force];
+    e = force == 0 ? launch_element<false, 0>(a, unsigned(n_wg), s)
+                   : (force == 1 ? launch_element<false, 1>(a, unsigned(n_wg), s) : launch_element<false, 2>(a, unsigned(n_wg), s));
+  }
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(estimate_sum_kernel, dim3(1), dim3(ESTIMATE_WG), 0, s, a.partial, n_wg, a.total);
+  return hipGetLastError();
+}
+
+}  // namespace dev
+}  // namespace hdd

@@ -252,6 +252,13 @@ def lib():
         "hdd_operator_solve_blocks_workspace": (_I64, [_I64, _I32, _I32]),
         "hdd_operator_solve_blocks": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _I64,
                                              _VP, _VP]),
+        "hdd_estimator_create": (_I32, [_VP, _VP, _VP]),
+        "hdd_estimator_destroy": (None, [_VP]),
+        "hdd_estimator_workspace": (_I64, [_VP]),
+        "hdd_estimator_set_residual_star": (_I32, [_VP, _I32]),
+        "hdd_swipdg_estimate": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP,
+                                       _VP, _VP, _VP]),
+        "hdd_last_estimate_kernels": (C.c_char_p, []),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -271,6 +278,12 @@ def last_solve_kernels():
     """hdd_last_solve_kernels: the kernels of one iteration of this thread's last solve, e.g.
     "apply_tile_kernel<3, 3, 1, dot> + cg_update<3> + cg_direction"""
     return lib().hdd_last_solve_kernels().decode()
+
+
+def last_estimate_kernels():
+    """hdd_last_estimate_kernels: the kernels of this thread's last estimate, e.g.
+    "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>"""
+    return lib().hdd_last_estimate_kernels().decode()
 
 
 def last_tile_kernel():
@@ -1183,6 +1196,96 @@ def solve_blocks(ctx, dpattern, vals, b, theta=None, dmesh=None, bounds=None, su
         i.history = None if hist is None else hist[j, :i.iterations + 1]
         out.append(i)
     return x, out
+
+
+# ----------------------------------------------------------------------------------------------------
+# a-posteriori error estimator
+# ----------------------------------------------------------------------------------------------------
+class Estimator:
+    """hdd_estimator: the per-mesh device tables of the ESV2007 estimator (vertex patches, boundary-vertex flags),
+    built once from the LocalMesh.  ctx None: host-only (sizes; no device).  Raises HddError (status 3) for what the
+    estimator does not cover: quadrilaterals, a view with ghosts, a Neumann face."""
+
+    def __init__(self, ctx, local):
+        h = C.c_void_p()
+        _check(lib().hdd_estimator_create(None if ctx is None else ctx.h, local.h, C.byref(h)), "hdd_estimator_create")
+        self.h = h
+        self.local = local
+        self.n_work = int(lib().hdd_estimator_workspace(self.h))
+        self.work = None
+
+    def set_residual_star(self, on=True):
+        """eta_R_ESV2007_* in place of eta_R in the estimates that follow: div t_h stands for the element mean of f"""
+        _check(lib().hdd_estimator_set_residual_star(self.h, int(bool(on))), "hdd_estimator_set_residual_star")
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            try:
+                lib().hdd_estimator_destroy(self.h)
+            except Exception:   # interpreter shutdown: module globals may already be gone
+                pass
+            self.h = None
+
+
+class Estimate:
+    """result of estimate(): sums [4] (the sums over T of eta_NC,T^2, eta_R,T^2, eta_DF,T^2, eta_T^2), eta_nc, eta_r,
+    eta_df, eta, eta_alt and, when asked for, the device tensors local [4, n], flux [3, n], oswald [n_vertices]"""
+
+    def __init__(self, sums, local, flux, oswald):
+        self.sums = sums
+        self.eta_nc, self.eta_r, self.eta_df = (float(np.sqrt(sums[k])) for k in range(3))
+        self.eta = float(np.sqrt(sums[3]))
+        self.eta_alt = self.eta_nc + self.eta_r + self.eta_df
+        self.local, self.flux, self.oswald = local, flux, oswald
+
+    def estimate_local(self, type="eta_ESV2007"):
+        """the reference's estimate_local: eta_T^2 / eta^2, or 3 (eta_NC,T^2 + eta_R,T^2 + eta_DF,T^2) / eta_alt^2"""
+        if self.local is None:
+            raise HddError("estimate_local: call estimate(..., local=True)")
+        if type == "eta_ESV2007":
+            return self.local[3] / self.eta ** 2
+        if type == "eta_ESV2007_alt":
+            return 3.0 * (self.local[0] + self.local[1] + self.local[2]) / self.eta_alt ** 2
+        raise HddError("estimate_local: type is eta_ESV2007 or eta_ESV2007_alt")
+
+
+def estimate(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=None, theta_bar=None, theta_hat=None, prm=None,
+             local=False, flux=False, oswald=False, stream=None):
+    """hdd_swipdg_estimate: the ESV2007 estimator of the P1 SWIPDG vector u (device float64 [3 n]) on the device.
+    est: the Estimator of dmesh's LocalMesh; kappas / tensor as assemble's (CONST / PER_ELEM components), theta_*
+    the parameters of the flux reconstruction (mu), the nonconformity (bar: None = mu) and the diffusive flux (hat:
+    None = mu); force: the scalar_fn of the right-hand side or None.  Returns an Estimate; local / flux / oswald ask
+    for the per-element arrays, the RT0 fluxes F_T,e and the Oswald vector.  Synchronises the stream once."""
+    torch = _torch()
+    kappas = list(kappas)
+    n = len(kappas)
+    dev = dmesh.coords.device
+    ne = dmesh.local.n_local
+    if u.dtype != torch.float64 or u.dim() != 1 or u.numel() != 3 * ne or (u.numel() > 1 and u.stride(0) != 1):
+        raise HddError("estimate: u must be float64 [%d] with unit stride" % (3 * ne))
+    if dmesh.vertex_coords is None:
+        raise HddError("estimate: the DeviceMesh must carry its vertex-indexed geometry")
+    arr = (ScalarFn * max(n, 1))(*kappas)
+    th = []
+    for t in (theta_mu, theta_bar, theta_hat):
+        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+        if t is not None and t.shape[0] != n:
+            raise HddError("estimate: every theta needs one entry per component")
+        th.append(t)
+    if est.work is None or est.work.device != dev:
+        est.work = torch.empty(max(est.n_work, 1), dtype=torch.float64, device=dev)
+    out_l = torch.empty((4, ne), dtype=torch.float64, device=dev) if local else None
+    out_f = torch.empty((3, ne), dtype=torch.float64, device=dev) if flux else None
+    out_o = torch.empty(dmesh.vertex_coords.shape[0], dtype=torch.float64, device=dev) if oswald else None
+    sums = np.zeros(4)
+    prm = prm or params_for(dmesh.local.degree, dmesh.local.dim)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _check(lib().hdd_swipdg_estimate(ctx.h, est.h, C.addressof(dmesh.t), arr, n, _p(th[0]), _p(th[1]), _p(th[2]),
+                                     C.addressof(tensor), None if force is None else C.addressof(force), C.addressof(prm),
+                                     u.data_ptr(), est.work.data_ptr(), est.n_work, ptr(out_l), ptr(out_f), ptr(out_o),
+                                     _p(sums), C.c_void_p(s)), "hdd_swipdg_estimate")
+    return Estimate(sums, out_l, out_f, out_o)
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

@@ -689,6 +689,82 @@ int hdd_operator_solve_blocks(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr*
                               int64_t n_work, double* d_history, int64_t ldh, hdd_solve_info* info, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- */
+/* a-posteriori error estimator -- Estimators::SWIPDG (estimators/swipdg.hh), which the reference's  */
+/* study calls right after every solve (test/linearelliptic-swipdg.hh:238-241, 302-315): the ESV2007   */
+/* estimator of a P1 SWIPDG vector, on the device where the solve left it.  Additive to ABI 8.        */
+/* ---------------------------------------------------------------------------------------------- */
+/* Scope: 2d HDD_SIMPLEX meshes, degree 1; the whole-grid view (own_begin == 0, own_end == n_local, no ghosts: a
+ * vertex patch needs every element around the vertex); every boundary face Dirichlet with g_D = 0 (the reference's
+ * Oswald operator assumes it); diffusion factor components HDD_FN_CONST or HDD_FN_PER_ELEM, combined as kappa_T(theta)
+ * = sum_q theta_q kappa_q,T; any tensor kind; a force of any hdd_scalar_fn kind (NULL: f = 0).  Everything else is
+ * HDD_ERR_UNSUPPORTED before the first device call, as the reference's `available = false` / NotImplemented.
+ *
+ * Definitions (u_h the P1 DG vector, DoF 3e + i at vertex elem_vertices[i][e]; K_T(theta) = kappa_T(theta) A_T):
+ *   I_OS u_h    Oswald interpolation: at a vertex the arithmetic mean of the DG values of the elements around it (taken
+ *               about the first of them in ascending element order: first + sum(u_k - first) / m), 0 at every vertex of
+ *               a boundary face
+ *   eta_NC,T^2  |T| g^T K_T(theta_bar) g, g = grad(u_h - I_OS u_h)
+ *   eta_R,T^2   h_T^2 / (pi^2 lambda_min(K_T(theta_mu))) int_T (f - P0 f)^2: h_T the longest edge, P0 f the element mean by
+ *               the simplex rule of order ord(f) + 2, the integral by the rule of order 2 ord(f) + 2; exactly 0 for a
+ *               CONST / PER_ELEM / absent force
+ *   F_T,e       the outward flux of the RT0 reconstruction t_h through face e with unit outer normal n,
+ *                 -|e| (w- K- grad u- + w+ K+ grad u+) . n + (sigma_inner gamma / |e|^beta) int_e (u- - u+)    interior
+ *                 -|e| K grad u . n + (sigma_boundary delta / |e|^beta) int_e u                                  boundary
+ *               delta+- = n . K+-(theta_mu) n, w- = delta+ / (delta+ + delta-), w+ = delta- / (delta+ + delta-), gamma =
+ *               delta+ delta- / (delta+ + delta-), sigma and beta from hdd_swipdg_params.  For kappa = 1 these are the
+ *               weights and the penalty of the scheme itself, and sum_e F_T,e is the sum of the three rows of element T
+ *               of (sum_q theta_mu,q A_q) u; for a kappa that varies the scheme takes delta from the tensor alone and
+ *               multiplies its penalty by kappa- kappa+, so the two differ (F_T,e + F_T',e' = 0 holds always);
+ *               t_h(x) = sum_e F_T,e / (2 |T|) (x - p_e), p_e the vertex opposite e
+ *   eta_DF,T^2  int_T (grad u_h + Khat^-1 t_h)^T Khat (grad u_h + Khat^-1 t_h), Khat = K_T(theta_hat), by the three edge
+ *               midpoints (exact)
+ *   eta_T^2     eta_NC,T^2 + (eta_R,T + eta_DF,T)^2
+ * so that eta_ESV2007 = sqrt(sums[3]) and eta_ESV2007_alt = sqrt(sums[0]) + sqrt(sums[1]) + sqrt(sums[2]). */
+typedef struct hdd_estimator hdd_estimator;
+/* Builds, once per mesh, the device tables of the kernels from the host view: the vertex -> (element, local vertex) CSR
+ * with entries in ascending element id and the boundary-vertex flags (12 B per element, 9 B per vertex).  The only
+ * place that allocates.  HDD_ERR_UNSUPPORTED (before the first device call) for a grid that is not a 2d simplex grid, a
+ * view with ghosts, a Neumann face.  ctx == NULL: a host-only estimator (sizes, no device tables), which
+ * hdd_estimator_workspace accepts and hdd_swipdg_estimate rejects after its other checks. */
+int hdd_estimator_create(hdd_ctx* ctx, const hdd_local* l, hdd_estimator** out);
+void hdd_estimator_destroy(hdd_estimator* est);
+/* doubles of caller workspace hdd_swipdg_estimate needs: the Oswald value of every vertex, four partial sums per 256
+ * elements and their totals; 0 for a null estimator */
+int64_t hdd_estimator_workspace(const hdd_estimator* est);
+/* on != 0: the calls that follow compute the reference's eta_R_ESV2007_* in place of eta_R (LocalResidualESV2007Star,
+ * estimators/swipdg.hh:320-470): div t_h = sum_e F_T,e / |T| stands for P0 f, eta_R*,T^2 = h_T^2 / (pi^2 lambda_min)
+ * int_T (f - div t_h)^2 by the rule of order 2 ord(f) + 2, for every force kind (an absent force is f = 0).  It takes
+ * the place of eta_R,T^2 in d_local, sums[1] and eta_T^2.  Default off. */
+int hdd_estimator_set_residual_star(hdd_estimator* est, int32_t on);
+/* mesh: the device mesh of the estimator's view, with elem_vertices / vertex_coords (HDD_ERR_INVALID without).  kappa
+ * [n_comp]; theta_mu (flux reconstruction, residual), theta_bar (nonconformity), theta_hat (diffusive flux): host
+ * [n_comp]; theta_mu == NULL: all ones, as in hdd_operator_apply; theta_bar / theta_hat == NULL: theta_mu.
+ * d_u: device [3 n].  d_work: device, n_work >= hdd_estimator_workspace doubles, 16-byte aligned.
+ * Outputs: d_local NULL or device [4][n] (eta_NC,T^2, eta_R,T^2, eta_DF,T^2, eta_T^2); d_flux NULL or device [3][n], F_T,e
+ * in the mesh's face order (the RT0 reconstruction itself: a conservative velocity field); d_oswald NULL or device
+ * [n_vertices]; sums host [4], the four sums over T.  What is computed does not depend on which outputs are NULL.
+ * Two launches (a lane per vertex, a lane per element) and the final reduction.  No atomics: the vertex means are a
+ * gather through the CSR and the sums are two-stage in a fixed order -- element e is lane e % 256 of workgroup e / 256,
+ * a workgroup adds v[t] += v[t + s] for s = 128 .. 1 (lanes without an element hold 0), then lane t of one workgroup
+ * adds the partial sums t, t + 256, ... in order and the same tree follows -- so every output is bit-identical from
+ * call to call.  Allocates nothing; SYNCHRONISES `stream` once to return the sums (through the pinned bytes the context
+ * owns since its creation); one stream at a time per context.
+ * HDD_ERR_INVALID (every argument check precedes the first device call) for a null ctx / est / mesh / kappa / tensor /
+ * params / d_u / d_work / sums, n_comp outside 1..HDD_MAX_COMP, a mesh of another size than the estimator's or without
+ * its vertex-indexed geometry, neighbours or face_info, a PER_ELEM function without values, n_work too small, a
+ * host-only estimator; HDD_ERR_UNSUPPORTED for quadrilaterals / hexahedra, degree > 1, a view with ghosts, a smooth
+ * kappa, a force whose two rules have more than 96 points together (ord(f) > 6). */
+int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* mesh, const hdd_scalar_fn* kappa,
+                        int32_t n_comp, const double* theta_mu, const double* theta_bar, const double* theta_hat,
+                        const hdd_tensor_fn* tensor, const hdd_scalar_fn* force, const hdd_swipdg_params* params,
+                        const double* d_u, double* d_work, int64_t n_work, double* d_local, double* d_flux,
+                        double* d_oswald, double* sums, void* stream);
+/* the kernels of this thread's last hdd_swipdg_estimate ("" if none), e.g.
+ * "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>" (beta == 1 is specialised: "pow" otherwise;
+ * the force: no_force, cos_product, generic_force) */
+const char* hdd_last_estimate_kernels(void);
+
+/* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */
 /* GPU owns a contiguous range of subdomains and assembles their rows -- A_ss and A_ss,nn are written  */
 /* by the owner of ss (block-swipdg.hh:355-382, coupling 1270-1326, boundary 1136-1179), so there is  */

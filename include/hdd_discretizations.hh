@@ -1299,6 +1299,108 @@ class SWIPDG {
     return *it->second;
   }
 
+  // Estimators::SWIPDG (estimators/swipdg.hh:921-984): the ESV2007 a-posteriori estimator of a solution vector, on the
+  // device (hdd_swipdg_estimate).  Available where the reference's is: the whole 2d conforming simplex grid with
+  // Dirichlet data on every boundary face; elsewhere the lists are empty and estimate() throws NotImplemented.
+  struct Estimate {
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};   // sums over T of eta_NC,T^2, eta_R,T^2 (or eta_R*,T^2), eta_DF,T^2, eta_T^2
+    std::vector<double> local;                // [4][n] when asked for
+    double eta_nc() const { return std::sqrt(sums[0]); }
+    double eta_r() const { return std::sqrt(sums[1]); }
+    double eta_df() const { return std::sqrt(sums[2]); }
+    double eta() const { return std::sqrt(sums[3]); }
+    double eta_alt() const { return eta_nc() + eta_r() + eta_df(); }
+  };
+  std::vector<std::string> available_estimators() const
+  {
+    if (!estimator_in_scope()) return {};
+    return {"eta_NC_ESV2007", "eta_R_ESV2007", "eta_R_ESV2007_*", "eta_DF_ESV2007", "eta_ESV2007", "eta_ESV2007_alt"};
+  }
+  std::vector<std::string> available_local_estimators() const
+  {
+    if (!estimator_in_scope()) return {};
+    return {"eta_ESV2007", "eta_ESV2007_alt"};
+  }
+  // the four sums (and the local arrays) of u at the parameters mu (flux reconstruction), mu_bar (nonconformity) and
+  // mu_hat (diffusive flux), which the reference reads from its parameter map as "mu", "mu_bar", "mu_hat";
+  // residual_star: eta_R_ESV2007_* (div t_h in place of the element mean of f) in place of eta_R
+  Estimate estimate_all(const std::vector<double>& u, double mu, double mu_bar, double mu_hat, bool residual_star = false,
+                        bool local = false) const
+  {
+    assert_everything_is_ready();
+    if (!estimator_in_scope())
+      throw NotImplemented("The ESV2007 estimator needs the whole 2d conforming simplex grid with Dirichlet data on "
+                           "every boundary face!");
+    if (problem_.force.parametric()) throw NotImplemented("Not implemented for parametric force!");
+    if (int64_t(u.size()) != pattern_->rows) throw Stuff::Exceptions::wrong_input_given("estimate: vector of wrong size");
+    if (!estimator_) {
+      hdd_estimator* est = nullptr;
+      internal::check(hdd_estimator_create(ctx_, local_, &est), "hdd_estimator_create");
+      estimator_ = std::shared_ptr<hdd_estimator>(est, hdd_estimator_destroy);
+      estimator_work_ = internal::DeviceArray<double>(size_t(hdd_estimator_workspace(est)) + 1);
+    }
+    const auto& K = problem_.diffusion_factor;
+    std::vector<detail::DeviceFn> fns;
+    std::vector<double> th[3];
+    if (K.has_affine_part) {
+      fns.emplace_back(K.affine_part, view_);
+      for (auto& t : th) t.push_back(1.0);
+    }
+    for (int q = 0; q < K.num_components(); ++q) {
+      fns.emplace_back(K.components[size_t(q)], view_);
+      th[0].push_back(K.coefficients[size_t(q)].evaluate(mu));
+      th[1].push_back(K.coefficients[size_t(q)].evaluate(mu_bar));
+      th[2].push_back(K.coefficients[size_t(q)].evaluate(mu_hat));
+    }
+    std::vector<hdd_scalar_fn> kappa;
+    for (const auto& f : fns) kappa.push_back(f.fn);
+    detail::DeviceFn force;
+    const bool has_force = problem_.force.has_affine_part && !problem_.force.affine_part.is_zero();
+    if (has_force) force = detail::DeviceFn(problem_.force.affine_part, view_);
+    internal::DeviceArray<double> d_u(u), d_local(local ? size_t(4 * linfo_.n_local) : 0);
+    Estimate out;
+    internal::check(hdd_estimator_set_residual_star(estimator_.get(), residual_star), "hdd_estimator_set_residual_star");
+    internal::check(hdd_swipdg_estimate(ctx_, estimator_.get(), &mesh_, kappa.data(), int32_t(kappa.size()), th[0].data(),
+                                        th[1].data(), th[2].data(), &tensor_.fn, has_force ? &force.fn : nullptr, &prm_,
+                                        d_u.get(), estimator_work_.get(), int64_t(estimator_work_.size()),
+                                        local ? d_local.get() : nullptr, nullptr, nullptr, out.sums, nullptr),
+                    "hdd_swipdg_estimate");
+    if (local) out.local = d_local.download();
+    return out;
+  }
+  // Estimators::SWIPDG::estimate(space, vector, problem, type): one of available_estimators()
+  double estimate(const std::vector<double>& u, const std::string& type, double mu = 0.0) const
+  {
+    return estimate(u, type, mu, mu, mu);
+  }
+  double estimate(const std::vector<double>& u, const std::string& type, double mu, double mu_bar, double mu_hat) const
+  {
+    const auto ids = available_estimators();
+    if (!ids.empty() && std::find(ids.begin(), ids.end(), type) == ids.end())
+      throw Stuff::Exceptions::you_are_using_this_wrong("Requested type '" + type + "' is not one of available()!");
+    const Estimate e = estimate_all(u, mu, mu_bar, mu_hat, type == "eta_R_ESV2007_*");
+    if (type == "eta_NC_ESV2007") return e.eta_nc();
+    if (type == "eta_R_ESV2007" || type == "eta_R_ESV2007_*") return e.eta_r();
+    if (type == "eta_DF_ESV2007") return e.eta_df();
+    return type == "eta_ESV2007" ? e.eta() : e.eta_alt();
+  }
+  // Estimators::SWIPDG::estimate_local: eta_T^2 / eta^2 ("eta_ESV2007") or 3 (eta_NC,T^2 + eta_R,T^2 + eta_DF,T^2) /
+  // eta_alt^2 ("eta_ESV2007_alt") per element -- what adaptive refinement marks by
+  std::vector<double> estimate_local(const std::vector<double>& u, const std::string& type, double mu = 0.0) const
+  {
+    const auto ids = available_local_estimators();
+    if (!ids.empty() && std::find(ids.begin(), ids.end(), type) == ids.end())
+      throw Stuff::Exceptions::you_are_using_this_wrong("Requested type '" + type + "' is not one of available_local()!");
+    const Estimate e = estimate_all(u, mu, mu, mu, false, true);
+    const size_t n = size_t(linfo_.n_local);
+    std::vector<double> out(n);
+    const bool alt = type == "eta_ESV2007_alt";
+    const double den = alt ? e.eta_alt() * e.eta_alt() : e.sums[3];
+    for (size_t k = 0; k < n; ++k)
+      out[k] = alt ? 3.0 * (e.local[k] + e.local[n + k] + e.local[2 * n + k]) / den : e.local[3 * n + k] / den;
+    return out;
+  }
+
   // true if no Dirichlet face was found (DirichletDetector, swipdg.hh:219, 488-489)
   bool purely_neumann() const
   {
@@ -1318,6 +1420,17 @@ class SWIPDG {
   {
     if (!initialized_)
       throw Stuff::Exceptions::you_are_using_this_wrong("The user has to call init() before calling any other method!");
+  }
+
+  // what hdd_swipdg_estimate covers, with the boundary info of this discretization applied
+  bool estimator_in_scope() const
+  {
+    if (info_.elem_type != HDD_SIMPLEX || info_.dim != 2 || layer_ != Layer::leaf || linfo_.n_ghost != 0 ||
+        linfo_.own_begin != 0)
+      return false;
+    for (const int32_t nb : nbrs_)
+      if (nb == HDD_NBR_NEUMANN) return false;
+    return true;
   }
 
   // host view of the elements: neighbour codes with the boundary info applied, columns (global / local)
@@ -1559,6 +1672,8 @@ class SWIPDG {
   AffinelyDecomposedMatrix matrix_;
   AffinelyDecomposedVector rhs_;
   std::map<std::string, std::shared_ptr<AffinelyDecomposedMatrix>> products_;
+  mutable std::shared_ptr<hdd_estimator> estimator_;          // built by the first estimate
+  mutable internal::DeviceArray<double> estimator_work_;
   bool initialized_ = false;
 };
 
