@@ -1,7 +1,11 @@
 // dune-hdd_amd/csrc/host/estimator_tables.cpp -- host tables of the ESV2007 estimator (hdd_estimator_create): the
 // vertex patches the Oswald interpolation gathers through and the boundary-vertex flags, built once per mesh from the
-// host view.  Pure host code: the scope checks of the estimator answer here, without a device.
+// host view; and the per-segment tables of the OS2014 block estimator (hdd_estimator_set_segments): bounds, chunk
+// prefix, diameters.  Pure host code: the scope checks of the estimator answer here, without a device.
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "hdd.h"
@@ -31,7 +35,8 @@ int estimator_tables(const hdd_local* l, EstimatorTables* out)
   int64_t nv = 0;
   if (int rc = hdd_local_vertices(l, &nv, nullptr, nullptr)) return rc;
   std::vector<int32_t> ev(size_t(3 * n));
-  if (int rc = hdd_local_vertices(l, &nv, ev.data(), nullptr)) return rc;
+  out->vertex_coords.resize(size_t(2 * nv));   // (kept with ev for the segment diameters: the same one pass)
+  if (int rc = hdd_local_vertices(l, &nv, ev.data(), out->vertex_coords.data())) return rc;
   out->n_local = n;
   out->n_vertices = nv;
   out->patch_ptr.assign(size_t(nv + 1), 0);
@@ -49,6 +54,90 @@ int estimator_tables(const hdd_local* l, EstimatorTables* out)
         out->vertex_bnd[ev[FV[f][0] * n + e]] = 1;
         out->vertex_bnd[ev[FV[f][1] * n + e]] = 1;
       }
+  out->elem_vertices.swap(ev);
+  return HDD_OK;
+}
+
+namespace {
+struct Pt {
+  double x, y;
+};
+
+// z of (a - o) x (b - o)
+inline double cross(const Pt& o, const Pt& a, const Pt& b) { return (a.x - o.x) * (b.y - o.y) - (a.y - o.y) * (b.x - o.x); }
+
+// the largest distance between two of the points (sorted in place): the pairwise maximum over their convex hull by
+// the monotone chain.  Collinear points leave the hull (a rectangle keeps its four corners), which keeps its extreme
+// points: the maximum is attained there.
+double diameter(std::vector<Pt>& pts, std::vector<Pt>& hull)
+{
+  std::sort(pts.begin(), pts.end(), [](const Pt& a, const Pt& b) { return a.x < b.x || (a.x == b.x && a.y < b.y); });
+  const size_t n = pts.size();
+  hull.clear();
+  if (n < 3) hull = pts;
+  else {
+    hull.resize(2 * n);
+    size_t k = 0;
+    for (size_t i = 0; i < n; ++i) {   // lower chain
+      while (k >= 2 && cross(hull[k - 2], hull[k - 1], pts[i]) <= 0.0) --k;
+      hull[k++] = pts[i];
+    }
+    for (size_t i = n - 1, lower = k + 1; i-- > 0;) {   // upper chain
+      while (k >= lower && cross(hull[k - 2], hull[k - 1], pts[i]) <= 0.0) --k;
+      hull[k++] = pts[i];
+    }
+    hull.resize(k - 1);   // the last point is the first again
+  }
+  double d = 0.0;
+  for (size_t i = 0; i < hull.size(); ++i)
+    for (size_t j = i + 1; j < hull.size(); ++j) {
+      const double dx = hull[i].x - hull[j].x, dy = hull[i].y - hull[j].y;
+      d = std::max(d, std::sqrt(dx * dx + dy * dy));
+    }
+  return d;
+}
+}  // namespace
+
+bool theta_positive(int32_t n_comp, const double* theta)
+{
+  for (int q = 0; q < n_comp; ++q)
+    if (!(theta[q] > 0.0)) return false;
+  return true;
+}
+
+int estimator_segment_tables(int64_t n_local, int64_t n_vertices, const int32_t* elem_vertices, const double* vertex_coords,
+                             int64_t n_segments, const int64_t* bounds, SegmentTables* out)
+{
+  static const char* who = "hdd_estimator_set_segments: ";
+  if (n_segments < 0) return set_error(HDD_ERR_INVALID, std::string(who) + "n_segments is negative");
+  if (!bounds) return set_error(HDD_ERR_INVALID, std::string(who) + "null bounds");
+  if (n_segments > n_local)
+    return set_error(HDD_ERR_INVALID, std::string(who) + "more segments than elements (every segment holds an element)");
+  if (bounds[0] != 0) return set_error(HDD_ERR_INVALID, std::string(who) + "bounds[0] is not 0");
+  for (int64_t s = 0; s < n_segments; ++s)
+    if (bounds[s + 1] <= bounds[s])
+      return set_error(HDD_ERR_INVALID, std::string(who) + "bounds are not strictly ascending (segment " +
+                                            std::to_string(s) + ")");
+  if (bounds[n_segments] != n_local)
+    return set_error(HDD_ERR_INVALID, std::string(who) + "bounds[n_segments] is not the number of elements: the segments "
+                                                          "partition [0, n)");
+  out->bounds.assign(bounds, bounds + n_segments + 1);
+  out->chunk_prefix.assign(size_t(n_segments + 1), 0);
+  out->diam.assign(size_t(n_segments), 0.0);
+  std::vector<int64_t> seen(size_t(n_vertices), -1);   // the last segment that met the vertex
+  std::vector<Pt> pts, hull;
+  for (int64_t s = 0; s < n_segments; ++s) {
+    out->chunk_prefix[s + 1] = out->chunk_prefix[s] + (bounds[s + 1] - bounds[s] + 255) / 256;
+    pts.clear();
+    for (int64_t e = bounds[s]; e < bounds[s + 1]; ++e)
+      for (int i = 0; i < 3; ++i) {
+        const int32_t v = elem_vertices[i * n_local + e];
+        if (seen[v] == s) continue;
+        seen[v] = s;
+        pts.push_back(Pt{vertex_coords[2 * int64_t(v)], vertex_coords[2 * int64_t(v) + 1]});
+      }
+    out->diam[s] = diameter(pts, hull);
+  }
   return HDD_OK;
 }
 

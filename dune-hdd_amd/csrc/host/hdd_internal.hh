@@ -26,8 +26,24 @@ struct EstimatorTables {
   std::vector<int64_t> patch_ptr;
   std::vector<int32_t> patch_dof;
   std::vector<uint8_t> vertex_bnd;
+  std::vector<int32_t> elem_vertices;   // [3][n_local]: kept for the segment diameters (hdd_estimator_set_segments)
+  std::vector<double> vertex_coords;    // [n_vertices][2]
 };
 int estimator_tables(const hdd_local* l, EstimatorTables* out);
+
+// Per-segment tables of the OS2014 block estimator (hdd_estimator_set_segments), from host element bounds
+// [n_segments + 1] (strictly ascending, bounds[0] == 0, bounds[S] == n_local; HDD_ERR_INVALID otherwise): the bounds,
+// the number of 256-element chunks before each segment, and diam_s, the largest distance between two vertices of the
+// segment's elements -- the pairwise maximum over the convex hull of the segment's distinct vertices (monotone
+// chain), O(V log V) where the reference's loop (block-swipdg.hh:293-303) is O(V^2).
+struct SegmentTables {
+  std::vector<int64_t> bounds, chunk_prefix;
+  std::vector<double> diam;
+};
+// every component > 0 (false for a NaN: this lives in host code built without -ffinite-math-only)
+bool theta_positive(int32_t n_comp, const double* theta);
+int estimator_segment_tables(int64_t n_local, int64_t n_vertices, const int32_t* elem_vertices, const double* vertex_coords,
+                             int64_t n_segments, const int64_t* bounds, SegmentTables* out);
 }  // namespace hdd
 
 // Sharded-step fixup off the assembly stream (abi_assemble.hip, used by shard_step.hip): the element-list pass into side

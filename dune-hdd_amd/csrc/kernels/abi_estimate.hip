@@ -1,5 +1,6 @@
-// dune-hdd_amd/csrc/kernels/abi_estimate.hip -- C ABI: the ESV2007 a-posteriori error estimator of P1 SWIPDG (kernels:
-// estimate.hip; host tables: csrc/host/estimator_tables.cpp)
+// dune-hdd_amd/csrc/kernels/abi_estimate.hip -- C ABI: the ESV2007 a-posteriori error estimator of P1 SWIPDG and the
+// OS2014 localized (per-segment) estimator of BlockSWIPDG (kernels: estimate.hip; host tables:
+// csrc/host/estimator_tables.cpp)
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,8 +22,26 @@ struct hdd_estimator {
   int64_t* patch_ptr = nullptr;    // device [n_vertices + 1]
   int32_t* patch_dof = nullptr;    // device [3 n_local]
   uint8_t* vertex_bnd = nullptr;   // device [n_vertices]
+  bool host_only = true;
+  // hdd_estimator_set_segments: host geometry (kept from the creation), host tables, device copies
+  std::vector<int32_t> elem_vertices;
+  std::vector<double> vertex_coords;
+  SegmentTables seg;
+  int64_t n_segments = 0, n_chunks = 0;
+  int64_t* seg_tab = nullptr;      // device [2][S + 1]: bounds, chunk prefix
+  double* seg_diam = nullptr;      // device [S]
+  void free_segments()
+  {
+    if (seg_tab) (void)hipFree(seg_tab);
+    if (seg_diam) (void)hipFree(seg_diam);
+    seg_tab = nullptr;
+    seg_diam = nullptr;
+    n_segments = n_chunks = 0;
+    seg = SegmentTables();
+  }
   ~hdd_estimator()
   {
+    free_segments();
     if (patch_ptr) (void)hipFree(patch_ptr);
     if (patch_dof) (void)hipFree(patch_dof);
     if (vertex_bnd) (void)hipFree(vertex_bnd);
@@ -40,6 +59,28 @@ const char*& last_estimate_kernels_slot()
 int64_t workspace_doubles(int64_t n_local, int64_t n_vertices)
 {
   return ((n_vertices + 1) & ~int64_t(1)) + 4 * dev::estimate_workgroups(n_local) + 4;
+}
+
+// the block call's: Oswald values, [4][n_chunks] partials, the four totals, [4][S] segment values
+int64_t blocks_workspace_doubles(const hdd_estimator* est)
+{
+  return ((est->n_vertices + 1) & ~int64_t(1)) + 4 * est->n_chunks + 4 + 4 * est->n_segments;
+}
+
+// theta of a role on the host: NULL -> fallback (NULL: all ones)
+void resolve_theta(int32_t n_comp, const double* th, const double* fallback, double* out)
+{
+  for (int q = 0; q < n_comp; ++q) out[q] = th ? th[q] : (fallback ? fallback[q] : 1.0);
+}
+
+// alpha(mu, mu') = min_q theta_q(mu) / theta_q(mu'), gamma = max_q of the same ratio
+void alpha_gamma(int32_t n_comp, const double* mu, const double* other, double* alpha, double* gamma)
+{
+  *alpha = *gamma = mu[0] / other[0];
+  for (int q = 1; q < n_comp; ++q) {
+    *alpha = std::min(*alpha, mu[q] / other[q]);
+    *gamma = std::max(*gamma, mu[q] / other[q]);
+  }
 }
 
 template <class T>
@@ -65,10 +106,13 @@ extern "C" int hdd_estimator_create(hdd_ctx* ctx, const hdd_local* l, hdd_estima
   if (!est) return fail(HDD_ERR_NOMEM, who, "out of host memory");
   est->n_local = t.n_local;
   est->n_vertices = t.n_vertices;
+  est->elem_vertices.swap(t.elem_vertices);
+  est->vertex_coords.swap(t.vertex_coords);
   *out = est;
   if (!ctx) return HDD_OK;   // host-only: sizes, no device tables
   *out = nullptr;
   est->device = ctx->device;
+  est->host_only = false;
   hipError_t e = hipSetDevice(ctx->device);
   if (e == hipSuccess) e = upload(&est->patch_ptr, t.patch_ptr);
   if (e == hipSuccess) e = upload(&est->patch_dof, t.patch_dof);
@@ -97,13 +141,15 @@ extern "C" int64_t hdd_estimator_workspace(const hdd_estimator* est)
 
 extern "C" const char* hdd_last_estimate_kernels(void) { return last_estimate_kernels_slot(); }
 
-extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* m, const hdd_scalar_fn* kappa,
-                                   int32_t n_comp, const double* theta_mu, const double* theta_bar,
-                                   const double* theta_hat, const hdd_tensor_fn* tensor, const hdd_scalar_fn* force,
-                                   const hdd_swipdg_params* p, const double* d_u, double* d_work, int64_t n_work,
-                                   double* d_local, double* d_flux, double* d_oswald, double* sums, void* stream)
+namespace {
+// the argument checks both estimate calls share (every one of them before the first device call) and the kernel
+// arguments they have in common; n_need: the workspace of the call
+int check_and_fill(const char* who, hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* m, const hdd_scalar_fn* kappa,
+                   int32_t n_comp, const double* theta_mu, const double* theta_bar, const double* theta_hat,
+                   const hdd_tensor_fn* tensor, const hdd_scalar_fn* force, const hdd_swipdg_params* p, const double* d_u,
+                   double* d_work, int64_t n_work, int64_t n_need, const char* need_name, double* d_local, double* d_flux,
+                   double* d_oswald, double* sums, dev::EstimateArgs& a)
 {
-  static const char* who = "hdd_swipdg_estimate";
   if (!ctx || !est || !m || !kappa || !tensor || !p || !d_u || !d_work || !sums)
     return fail(HDD_ERR_INVALID, who, "null argument");
   if (n_comp < 1 || n_comp > HDD_MAX_COMP) return fail(HDD_ERR_INVALID, who, "n_comp outside 1..HDD_MAX_COMP");
@@ -127,10 +173,8 @@ extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const
   if (force && (force->kind < HDD_FN_CONST || force->kind > HDD_FN_FLATTOP))
     return fail(HDD_ERR_UNSUPPORTED, who, "unknown force kind");
   if (!(p->beta == p->beta)) return fail(HDD_ERR_INVALID, who, "beta is NaN");
-  if (n_work < workspace_doubles(est->n_local, est->n_vertices))
-    return fail(HDD_ERR_INVALID, who, "n_work below hdd_estimator_workspace");
+  if (n_work < n_need) return fail(HDD_ERR_INVALID, who, need_name);
 
-  dev::EstimateArgs a{};
   a.n = m->n_local;
   a.n_vertices = est->n_vertices;
   a.ev = m->elem_vertices;
@@ -142,8 +186,6 @@ extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const
   a.vertex_bnd = est->vertex_bnd;
   a.u = d_u;
   a.oswald = d_work;
-  a.partial = d_work + ((est->n_vertices + 1) & ~int64_t(1));
-  a.total = a.partial + 4 * dev::estimate_workgroups(a.n);
   a.out_local = d_local;
   a.out_flux = d_flux;
   a.out_oswald = d_oswald;
@@ -189,6 +231,34 @@ extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const
   a.beta = p->beta;
   a.beta_is_one = p->beta == 1.0;
 
+  return HDD_OK;
+}
+
+// the launches are over: the four totals come back through the context's pinned bytes (one synchronisation)
+int fetch_sums(const char* where, hdd_ctx* ctx, const dev::EstimateArgs& a, hipStream_t s, double* sums)
+{
+  hipError_t e = hipMemcpyAsync(ctx->solve_state_h, a.total, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
+  if (e == hipSuccess) e = hipStreamSynchronize(s);
+  if (e != hipSuccess) return hip_fail(e, where);
+  for (int r = 0; r < 4; ++r) sums[r] = ctx->solve_state_h[r];
+  return HDD_OK;
+}
+}  // namespace
+
+extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* m, const hdd_scalar_fn* kappa,
+                                   int32_t n_comp, const double* theta_mu, const double* theta_bar,
+                                   const double* theta_hat, const hdd_tensor_fn* tensor, const hdd_scalar_fn* force,
+                                   const hdd_swipdg_params* p, const double* d_u, double* d_work, int64_t n_work,
+                                   double* d_local, double* d_flux, double* d_oswald, double* sums, void* stream)
+{
+  static const char* who = "hdd_swipdg_estimate";
+  dev::EstimateArgs a{};
+  if (int rc = check_and_fill(who, ctx, est, m, kappa, n_comp, theta_mu, theta_bar, theta_hat, tensor, force, p, d_u, d_work,
+                              n_work, est ? workspace_doubles(est->n_local, est->n_vertices) : 0,
+                              "n_work below hdd_estimator_workspace", d_local, d_flux, d_oswald, sums, a))
+    return rc;
+  a.partial = d_work + ((est->n_vertices + 1) & ~int64_t(1));
+  a.total = a.partial + 4 * dev::estimate_workgroups(a.n);
   if (!est->patch_ptr) return fail(HDD_ERR_INVALID, who, "host-only estimator (created without a context)");
   if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
   hipError_t e = hipSetDevice(ctx->device);
@@ -196,9 +266,123 @@ extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const
   const hipStream_t s = static_cast<hipStream_t>(stream);
   e = dev::launch_estimate(a, s, &last_estimate_kernels_slot());
   if (e != hipSuccess) return hip_fail(e, "hdd_swipdg_estimate: launch");
-  e = hipMemcpyAsync(ctx->solve_state_h, a.total, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(e, "hdd_swipdg_estimate: sums");
-  for (int r = 0; r < 4; ++r) sums[r] = ctx->solve_state_h[r];
+  return fetch_sums("hdd_swipdg_estimate: sums", ctx, a, s, sums);
+}
+
+extern "C" int hdd_estimator_set_segments(hdd_estimator* est, int64_t n_segments, const int64_t* bounds)
+{
+  static const char* who = "hdd_estimator_set_segments";
+  if (!est) return fail(HDD_ERR_INVALID, who, "null estimator");
+  if (n_segments == 0) {
+    if (!est->host_only) {
+      const hipError_t e = hipSetDevice(est->device);
+      if (e != hipSuccess) return hip_fail(e, "hdd_estimator_set_segments: hipSetDevice");
+    }
+    est->free_segments();
+    return HDD_OK;
+  }
+  SegmentTables t;
+  if (int rc = estimator_segment_tables(est->n_local, est->n_vertices, est->elem_vertices.data(), est->vertex_coords.data(),
+                                        n_segments, bounds, &t))
+    return rc;   // (the tables of the last valid call stay)
+  int64_t* tab = nullptr;
+  double* diam = nullptr;
+  if (!est->host_only) {
+    hipError_t e = hipSetDevice(est->device);
+    std::vector<int64_t> both(t.bounds);
+    both.insert(both.end(), t.chunk_prefix.begin(), t.chunk_prefix.end());
+    if (e == hipSuccess) e = upload(&tab, both);
+    if (e == hipSuccess) e = upload(&diam, t.diam);
+    if (e != hipSuccess) {
+      if (tab) (void)hipFree(tab);
+      if (diam) (void)hipFree(diam);
+      return hip_fail(e, "hdd_estimator_set_segments: tables");
+    }
+  }
+  est->free_segments();
+  est->seg.bounds.swap(t.bounds);
+  est->seg.chunk_prefix.swap(t.chunk_prefix);
+  est->seg.diam.swap(t.diam);
+  est->n_segments = n_segments;
+  est->n_chunks = est->seg.chunk_prefix[size_t(n_segments)];
+  est->seg_tab = tab;
+  est->seg_diam = diam;
   return HDD_OK;
+}
+
+extern "C" int hdd_estimator_segment_diameters(const hdd_estimator* est, double* out)
+{
+  static const char* who = "hdd_estimator_segment_diameters";
+  if (!est || !out) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (est->n_segments == 0) return fail(HDD_ERR_INVALID, who, "no segments set (hdd_estimator_set_segments)");
+  std::copy(est->seg.diam.begin(), est->seg.diam.end(), out);
+  return HDD_OK;
+}
+
+extern "C" int64_t hdd_estimator_blocks_workspace(const hdd_estimator* est)
+{
+  return est && est->n_segments > 0 ? blocks_workspace_doubles(est) : 0;
+}
+
+extern "C" int hdd_os2014_factors(int32_t n_comp, const double* theta_mu, const double* theta_bar, const double* theta_hat,
+                                  double out[5])
+{
+  static const char* who = "hdd_os2014_factors";
+  if (!out) return fail(HDD_ERR_INVALID, who, "null argument");
+  if (n_comp < 1 || n_comp > HDD_MAX_COMP) return fail(HDD_ERR_INVALID, who, "n_comp outside 1..HDD_MAX_COMP");
+  double th[3][HDD_MAX_COMP];
+  resolve_theta(n_comp, theta_mu, nullptr, th[0]);
+  resolve_theta(n_comp, theta_bar, theta_mu, th[1]);
+  resolve_theta(n_comp, theta_hat, theta_mu, th[2]);
+  for (int r = 0; r < 3; ++r)
+    if (!theta_positive(n_comp, th[r])) return fail(HDD_ERR_INVALID, who, "a theta component is not positive");
+  alpha_gamma(n_comp, th[0], th[1], &out[0], &out[1]);
+  alpha_gamma(n_comp, th[0], th[2], &out[2], &out[3]);
+  out[4] = std::max(std::sqrt(out[3]), 1.0 / std::sqrt(out[2]));
+  return HDD_OK;
+}
+
+extern "C" int hdd_block_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* m,
+                                         const hdd_scalar_fn* kappa, int32_t n_comp, const double* theta_mu,
+                                         const double* theta_bar, const double* theta_hat, const double* theta_min,
+                                         const double* theta_max, const hdd_tensor_fn* tensor, const hdd_scalar_fn* force,
+                                         const hdd_swipdg_params* p, const double* d_u, double* d_work, int64_t n_work,
+                                         double* d_local, double* d_flux, double* d_oswald, double* d_segments,
+                                         double* sums, void* stream)
+{
+  static const char* who = "hdd_block_swipdg_estimate";
+  if (est && est->n_segments == 0) return fail(HDD_ERR_INVALID, who, "no segments set (hdd_estimator_set_segments)");
+  dev::EstimateArgs a{};
+  if (int rc = check_and_fill(who, ctx, est, m, kappa, n_comp, theta_mu, theta_bar, theta_hat, tensor, force, p, d_u, d_work,
+                              n_work, est ? blocks_workspace_doubles(est) : 0,
+                              "n_work below hdd_estimator_blocks_workspace", d_local, d_flux, d_oswald, sums, a))
+    return rc;
+  resolve_theta(n_comp, theta_min, theta_mu, a.theta[3]);
+  resolve_theta(n_comp, theta_max, theta_mu, a.theta[4]);
+  for (int r = 0; r < 5; ++r)
+    if (!theta_positive(n_comp, a.theta[r]))
+      return fail(HDD_ERR_INVALID, who, "a theta component is not positive (mu, mu_bar, mu_hat, mu_min, mu_max)");
+  double f[5];
+  if (int rc = hdd_os2014_factors(n_comp, a.theta[0], a.theta[1], a.theta[2], f)) return rc;
+  a.factor[0] = std::sqrt(f[1]);
+  a.factor[1] = f[4];
+  a.factor[2] = 1.0 / std::sqrt(f[0]);
+  const int64_t S = est->n_segments;
+  a.n_segments = S;
+  a.n_chunks = est->n_chunks;
+  a.seg_bounds = est->seg_tab;
+  a.chunk_prefix = est->seg_tab + (S + 1);
+  a.seg_diam = est->seg_diam;
+  a.partial = d_work + ((est->n_vertices + 1) & ~int64_t(1));
+  a.total = a.partial + 4 * a.n_chunks;
+  a.segments = d_segments ? d_segments : a.total + 4;
+  if (!est->patch_ptr || !est->seg_tab)
+    return fail(HDD_ERR_INVALID, who, "host-only estimator (created without a context)");
+  if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, "hdd_block_swipdg_estimate: hipSetDevice");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  e = dev::launch_estimate_blocks(a, s, &last_estimate_kernels_slot());
+  if (e != hipSuccess) return hip_fail(e, "hdd_block_swipdg_estimate: launch");
+  return fetch_sums("hdd_block_swipdg_estimate: sums", ctx, a, s, sums);
 }

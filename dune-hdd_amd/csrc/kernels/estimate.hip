@@ -1,5 +1,6 @@
-// dune-hdd_amd/csrc/kernels/estimate.hip -- kernels of the ESV2007 estimator (estimate_kernels.hh has the launch
-// structure and the order of every sum; hdd.h hdd_swipdg_estimate the definitions).
+// dune-hdd_amd/csrc/kernels/estimate.hip -- kernels of the ESV2007 estimator and of the OS2014 block estimator
+// (estimate_kernels.hh has the launch structures and the order of every sum; hdd.h hdd_swipdg_estimate and
+// hdd_block_swipdg_estimate the definitions).
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -91,8 +92,16 @@ __device__ __forceinline__ double force_at(const EstimateArgs& a, int64_t e, con
   else return fn_value(a.force, e, x, 2);
 }
 
-// h_T^2 / (pi^2 lambda_min(K)) int_T (f - P0 f)^2; with residual_star div t_h (constant on T) stands for P0 f
-template <int FORCE>
+// lambda_min of the symmetric 2 x 2 tensor (k11, k12, k22)
+__device__ __forceinline__ double lambda_min(const double K[3])
+{
+  const double hd = 0.5 * (K[0] - K[2]);
+  return 0.5 * (K[0] + K[2]) - sqrt(hd * hd + K[1] * K[1]);
+}
+
+// h_T^2 / (pi^2 lambda_min(K)) int_T (f - P0 f)^2; with residual_star div t_h (constant on T) stands for P0 f.
+// RAW (block mode): the integral alone, r_T of the OS2014 residual
+template <int FORCE, bool RAW>
 __device__ __forceinline__ double residual2(const EstimateArgs& a, int64_t e, const double p[3][2], double det,
                                             const double K[3], double div)
 {
@@ -112,6 +121,7 @@ __device__ __forceinline__ double residual2(const EstimateArgs& a, int64_t e, co
     const double d = force_at<FORCE>(a, e, x) - mean;
     s += a.q[k][2] * (d * d);
   }
+  if constexpr (RAW) return fabs(det) * s;
   double h2 = 0.0;
 #pragma unroll
   for (int f = 0; f < 3; ++f) {
@@ -119,8 +129,7 @@ __device__ __forceinline__ double residual2(const EstimateArgs& a, int64_t e, co
     const double tx = p[j][0] - p[i][0], ty = p[j][1] - p[i][1];
     h2 = fmax(h2, tx * tx + ty * ty);
   }
-  const double hd = 0.5 * (K[0] - K[2]);
-  const double lam = 0.5 * (K[0] + K[2]) - sqrt(hd * hd + K[1] * K[1]);
+  const double lam = lambda_min(K);
   return h2 / (9.8696044010893586188 * lam) * (fabs(det) * s);
 }
 
@@ -164,33 +173,52 @@ __device__ __forceinline__ double face_flux(const EstimateArgs& a, int64_t e, ui
   return -le * ((wm * Kg[0] + wp * Kgp0) * nx + (wm * Kg[1] + wp * Kgp1) * ny) + pen * (mean_m - mean_p);
 }
 
-// v[t] += v[t + s], s = ESTIMATE_WG / 2 .. 1, on the four rows of sh; the sums end in sh[k][0]
+// v[t] += v[t + s], s = ESTIMATE_WG / 2 .. 1, on the four rows of sh; the sums end in sh[k][0].  MIN3: the fourth row
+// takes the minimum in place of the sum
+template <bool MIN3 = false>
 __device__ __forceinline__ void tree_sum(double (*sh)[ESTIMATE_WG], int t)
 {
   for (int s = ESTIMATE_WG / 2; s >= 1; s >>= 1) {
     __syncthreads();
     if (t < s) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) sh[k][t] += sh[k][t + s];
+      for (int k = 0; k < (MIN3 ? 3 : 4); ++k) sh[k][t] += sh[k][t + s];
+      if (MIN3) sh[3][t] = fmin(sh[3][t], sh[3][t + s]);
     }
   }
   __syncthreads();
 }
 
-// FORCE: 0 no residual term, 1 HDD_FN_COS_PRODUCT inline, 2 any kind through fn_value
-template <bool BETA1, int FORCE>
+// the neutral element of the minimum of m_T (finite: the kernels are built with -ffinite-math-only)
+constexpr double NO_MINIMUM = 1.7976931348623157e308;
+
+// FORCE: 0 no residual term, 1 HDD_FN_COS_PRODUCT inline, 2 any kind through fn_value.  BLOCK: the workgroup is a chunk
+// of 256 elements of a segment; rows 1 and 3 are r_T and m_T (estimate_kernels.hh)
+template <bool BETA1, int FORCE, bool BLOCK>
 __global__ void __launch_bounds__(ESTIMATE_WG) esv2007_element_kernel(const EstimateArgs a)
 {
   __shared__ double sh[4][ESTIMATE_WG];
   const int t = threadIdx.x;
-  const int64_t e = int64_t(blockIdx.x) * ESTIMATE_WG + t;
-  double eta[4] = {0.0, 0.0, 0.0, 0.0};
-  if (e < a.n) {
+  int64_t e = int64_t(blockIdx.x) * ESTIMATE_WG + t, end = a.n;
+  if constexpr (BLOCK) {
+    // the segment of chunk blockIdx.x: chunk_prefix[s] <= blockIdx.x < chunk_prefix[s + 1] (uniform: scalar loads)
+    int64_t lo = 0, hi = a.n_segments;
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (a.chunk_prefix[mid] <= int64_t(blockIdx.x)) lo = mid;
+      else hi = mid;
+    }
+    e = a.seg_bounds[lo] + (int64_t(blockIdx.x) - a.chunk_prefix[lo]) * ESTIMATE_WG + t;
+    end = a.seg_bounds[lo + 1];
+  }
+  double eta[4] = {0.0, 0.0, 0.0, BLOCK ? NO_MINIMUM : 0.0};
+  if (e < end) {
+    constexpr int NR = BLOCK ? 5 : 3;
     int32_t v[3];
-    double p[3][2], w[3], A[3], k[3];
+    double p[3][2], w[3], A[3], k[NR];
     load_element(a, e, v, p, w);
     tensor_of(a, e, A);
-    kappa_of<3>(a, e, k);
+    kappa_of<NR>(a, e, k);
     const double det = tri_det(p), area = 0.5 * fabs(det);
     const double Kmu[3] = {k[0] * A[0], k[0] * A[1], k[0] * A[2]};
     double g[2];
@@ -224,9 +252,13 @@ __global__ void __launch_bounds__(ESTIMATE_WG) esv2007_element_kernel(const Esti
       }
       eta[2] = s;
     }
-    if (FORCE != 0) eta[1] = residual2<FORCE>(a, e, p, det, Kmu, (F[0] + F[1] + F[2]) / area);
-    const double rd = sqrt(fmax(eta[1], 0.0)) + sqrt(fmax(eta[2], 0.0));
-    eta[3] = eta[0] + rd * rd;
+    if (FORCE != 0) eta[1] = residual2<FORCE, BLOCK>(a, e, p, det, Kmu, (F[0] + F[1] + F[2]) / area);
+    if constexpr (BLOCK) {
+      eta[3] = fmin(k[3], k[4]) * lambda_min(A);
+    } else {
+      const double rd = sqrt(fmax(eta[1], 0.0)) + sqrt(fmax(eta[2], 0.0));
+      eta[3] = eta[0] + rd * rd;
+    }
     if (a.out_local) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) a.out_local[r * a.n + e] = eta[r];
@@ -238,8 +270,60 @@ __global__ void __launch_bounds__(ESTIMATE_WG) esv2007_element_kernel(const Esti
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) sh[r][t] = eta[r];
-  tree_sum(sh, t);
+  tree_sum<BLOCK>(sh, t);
   if (t < 4) a.partial[int64_t(t) * gridDim.x + blockIdx.x] = sh[t][0];
+}
+
+// Block mode, workgroup s: the chunk partials of segment s in the order of a fixed_order_sum of its elements (lane t
+// adds the chunks t, t + 256, ... in order, then the tree; one chunk + zeros is that chunk exactly), the minimum of
+// m_T, and from them N_s, R_s, D_s and the indicator before its division by eta^2
+__global__ void __launch_bounds__(ESTIMATE_WG) block_segment_kernel(const EstimateArgs a)
+{
+  __shared__ double sh[4][ESTIMATE_WG];
+  const int t = threadIdx.x;
+  const int64_t s = blockIdx.x, S = a.n_segments, C = a.n_chunks;
+  const int64_t c0 = a.chunk_prefix[s], c1 = a.chunk_prefix[s + 1];
+  double acc[4] = {0.0, 0.0, 0.0, NO_MINIMUM};
+  for (int64_t c = c0 + t; c < c1; c += ESTIMATE_WG) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r) acc[r] += a.partial[r * C + c];
+    acc[3] = fmin(acc[3], a.partial[3 * C + c]);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) sh[r][t] = acc[r];
+  tree_sum<true>(sh, t);
+  if (t == 0) {
+    const double d = a.seg_diam[s];
+    const double N = sh[0][0], D = sh[2][0];
+    const double R = d * d / (9.8696044010893586188 * sh[3][0]) * sh[1][0];
+    a.segments[s] = N;
+    a.segments[S + s] = R;
+    a.segments[2 * S + s] = D;
+    a.segments[3 * S + s] = 3.0 * a.factor[2] * (a.factor[0] * N + R + a.factor[1] * D);
+  }
+}
+
+// Block mode, one workgroup: lane t adds N_s, R_s, D_s of the segments t, t + 256, ... in order, then the tree; eta^2 =
+// (1 / sqrt(alpha) (sqrt(gamma) eta_NC + eta_R + gamma~ eta_DF))^2; the indicators are divided by it
+__global__ void __launch_bounds__(ESTIMATE_WG) block_total_kernel(const EstimateArgs a)
+{
+  __shared__ double sh[4][ESTIMATE_WG];
+  const int t = threadIdx.x;
+  const int64_t S = a.n_segments;
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    double acc = 0.0;
+    for (int64_t s = t; s < S; s += ESTIMATE_WG) acc += a.segments[r * S + s];
+    sh[r][t] = acc;
+  }
+  sh[3][t] = 0.0;
+  tree_sum(sh, t);
+  const double eta = a.factor[2] * (a.factor[0] * sqrt(sh[0][0]) + sqrt(sh[1][0]) + a.factor[1] * sqrt(sh[2][0]));
+  const double eta2 = eta * eta;
+  if (t < 3) a.total[t] = sh[t][0];
+  if (t == 3) a.total[3] = eta2;
+  // eta = 0 (a conforming u_h with vanishing flux misfit and no residual): every N_s, R_s, D_s is 0, and so is the indicator
+  for (int64_t s = t; s < S; s += ESTIMATE_WG) a.segments[3 * S + s] = eta2 > 0.0 ? a.segments[3 * S + s] / eta2 : 0.0;
 }
 
 __global__ void __launch_bounds__(ESTIMATE_WG) estimate_sum_kernel(const double* __restrict__ partial, int64_t n_wg,
@@ -257,26 +341,61 @@ __global__ void __launch_bounds__(ESTIMATE_WG) estimate_sum_kernel(const double*
   if (t < 4) total[t] = sh[t][0];
 }
 
-template <bool BETA1, int FORCE>
+template <bool BETA1, int FORCE, bool BLOCK = false>
 hipError_t launch_element(const EstimateArgs& a, unsigned n_wg, hipStream_t s)
 {
-  hipLaunchKernelGGL((esv2007_element_kernel<BETA1, FORCE>), dim3(n_wg), dim3(ESTIMATE_WG), 0, s, a);
+  hipLaunchKernelGGL((esv2007_element_kernel<BETA1, FORCE, BLOCK>), dim3(n_wg), dim3(ESTIMATE_WG), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_oswald(const EstimateArgs& a, hipStream_t s)
+{
+  const int64_t v_wg = (a.n_vertices + ESTIMATE_WG - 1) / ESTIMATE_WG;
+  if (v_wg <= 0) return hipSuccess;
+  hipLaunchKernelGGL(oswald_vertex_kernel, dim3(unsigned(v_wg)), dim3(ESTIMATE_WG), 0, s, a.n_vertices, a.patch_ptr,
+                     a.patch_dof, a.vertex_bnd, a.u, a.oswald, a.out_oswald);
   return hipGetLastError();
 }
 
 }  // namespace
 
+hipError_t launch_estimate_blocks(const EstimateArgs& a, hipStream_t s, const char** names)
+{
+  hipError_t e = launch_oswald(a, s);
+  if (e != hipSuccess) return e;
+  const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
+  const unsigned n_wg = unsigned(a.n_chunks);
+  static const char* nm[2][3] = {
+      {"oswald_vertex_kernel + esv2007_element_kernel<pow, no_force, block> + block_segment_kernel + block_total_kernel",
+       "oswald_vertex_kernel + esv2007_element_kernel<pow, cos_product, block> + block_segment_kernel + block_total_kernel",
+       "oswald_vertex_kernel + esv2007_element_kernel<pow, generic_force, block> + block_segment_kernel + "
+       "block_total_kernel"},
+      {"oswald_vertex_kernel + esv2007_element_kernel<beta1, no_force, block> + block_segment_kernel + block_total_kernel",
+       "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product, block> + block_segment_kernel + "
+       "block_total_kernel",
+       "oswald_vertex_kernel + esv2007_element_kernel<beta1, generic_force, block> + block_segment_kernel + "
+       "block_total_kernel"}};
+  *names = nm[a.beta_is_one ? 1 : 0][force];
+  if (a.beta_is_one)
+    e = force == 0 ? launch_element<true, 0, true>(a, n_wg, s)
+                   : (force == 1 ? launch_element<true, 1, true>(a, n_wg, s) : launch_element<true, 2, true>(a, n_wg, s));
+  else
+    e = force == 0 ? launch_element<false, 0, true>(a, n_wg, s)
+                   : (force == 1 ? launch_element<false, 1, true>(a, n_wg, s) : launch_element<false, 2, true>(a, n_wg, s));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(block_segment_kernel, dim3(unsigned(a.n_segments)), dim3(ESTIMATE_WG), 0, s, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(block_total_kernel, dim3(1), dim3(ESTIMATE_WG), 0, s, a);
+  return hipGetLastError();
+}
+
 hipError_t launch_estimate(const EstimateArgs& a, hipStream_t s, const char** names)
 {
-  const int64_t n_wg = estimate_workgroups(a.n), v_wg = (a.n_vertices + ESTIMATE_WG - 1) / ESTIMATE_WG;
-  if (v_wg > 0) {
-    hipLaunchKernelGGL(oswald_vertex_kernel, dim3(unsigned(v_wg)), dim3(ESTIMATE_WG), 0, s, a.n_vertices, a.patch_ptr,
-                       a.patch_dof, a.vertex_bnd, a.u, a.oswald, a.out_oswald);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-  }
+  const int64_t n_wg = estimate_workgroups(a.n);
+  hipError_t e = launch_oswald(a, s);
+  if (e != hipSuccess) return e;
   const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
-  hipError_t e;
   if (a.beta_is_one) {
     static const char* nm[3] = {"oswald_vertex_kernel + esv2007_element_kernel<beta1, no_force>",
                                 "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>",

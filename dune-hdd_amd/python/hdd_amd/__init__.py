@@ -259,6 +259,12 @@ def lib():
         "hdd_swipdg_estimate": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP,
                                        _VP, _VP, _VP]),
         "hdd_last_estimate_kernels": (C.c_char_p, []),
+        "hdd_estimator_set_segments": (_I32, [_VP, _I64, _VP]),
+        "hdd_estimator_segment_diameters": (_I32, [_VP, _VP]),
+        "hdd_estimator_blocks_workspace": (_I64, [_VP]),
+        "hdd_os2014_factors": (_I32, [_I32, _VP, _VP, _VP, _VP]),
+        "hdd_block_swipdg_estimate": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                             _I64, _VP, _VP, _VP, _VP, _VP, _VP]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -1213,10 +1219,38 @@ class Estimator:
         self.local = local
         self.n_work = int(lib().hdd_estimator_workspace(self.h))
         self.work = None
+        self.n_segments, self.n_work_blocks = 0, 0
 
     def set_residual_star(self, on=True):
         """eta_R_ESV2007_* in place of eta_R in the estimates that follow: div t_h stands for the element mean of f"""
         _check(lib().hdd_estimator_set_residual_star(self.h, int(bool(on))), "hdd_estimator_set_residual_star")
+
+    def set_segments(self, bounds=None, subdomains=None):
+        """hdd_estimator_set_segments: the segments of estimate_blocks, element bounds [S + 1] of the whole-grid view
+        (strictly ascending from 0 to n), or subdomains=(s0, s1): one segment per subdomain of that range
+        (Grid.subdomain_range).  Builds the per-segment tables (chunk prefix, diameters).  Neither: clears them."""
+        if subdomains is not None:
+            if bounds is not None:
+                raise HddError("set_segments: give bounds or subdomains, not both")
+            s0, s1 = subdomains
+            bounds = [self.local.grid.subdomain_range(s0, s0 + 1)[0]]
+            bounds += [self.local.grid.subdomain_range(s, s + 1)[1] for s in range(s0, s1)]
+        if bounds is None:
+            _check(lib().hdd_estimator_set_segments(self.h, 0, None), "hdd_estimator_set_segments")
+            self.n_segments, self.n_work_blocks = 0, 0
+            return
+        b = np.ascontiguousarray(bounds, np.int64).reshape(-1)
+        if b.shape[0] < 2:
+            raise HddError("set_segments: bounds needs at least two entries")
+        _check(lib().hdd_estimator_set_segments(self.h, b.shape[0] - 1, _p(b)), "hdd_estimator_set_segments")
+        self.n_segments = b.shape[0] - 1
+        self.n_work_blocks = int(lib().hdd_estimator_blocks_workspace(self.h))
+
+    def segment_diameters(self):
+        """hdd_estimator_segment_diameters: the largest vertex distance of every segment, float64 [S] (host)"""
+        out = np.zeros(max(getattr(self, "n_segments", 0), 1))
+        _check(lib().hdd_estimator_segment_diameters(self.h, _p(out)), "hdd_estimator_segment_diameters")
+        return out[:self.n_segments]
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -1286,6 +1320,87 @@ def estimate(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=None, thet
                                      u.data_ptr(), est.work.data_ptr(), est.n_work, ptr(out_l), ptr(out_f), ptr(out_o),
                                      _p(sums), C.c_void_p(s)), "hdd_swipdg_estimate")
     return Estimate(sums, out_l, out_f, out_o)
+
+
+def os2014_factors(theta_mu, theta_bar=None, theta_hat=None):
+    """hdd_os2014_factors: (alpha(mu, mu_bar), gamma(mu, mu_bar), alpha(mu, mu_hat), gamma(mu, mu_hat), gamma_tilde) of
+    the OS2014 estimator, alpha = min_q theta_q(mu) / theta_q(mu'), gamma = max_q, gamma_tilde = max(sqrt(gamma(mu,
+    mu_hat)), 1 / sqrt(alpha(mu, mu_hat))); theta_bar / theta_hat None: theta_mu"""
+    mu = np.ascontiguousarray(theta_mu, np.float64).reshape(-1)
+    th = [mu]
+    for t in (theta_bar, theta_hat):
+        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+        if t is not None and t.shape[0] != mu.shape[0]:
+            raise HddError("os2014_factors: every theta needs one entry per component")
+        th.append(t)
+    out = np.zeros(5)
+    _check(lib().hdd_os2014_factors(mu.shape[0], _p(th[0]), _p(th[1]), _p(th[2]), _p(out)), "hdd_os2014_factors")
+    return tuple(float(v) for v in out)
+
+
+class BlockEstimate:
+    """result of estimate_blocks(): sums [4] (sum N_s, sum R_s, sum D_s, eta^2), eta_nc, eta_r, eta_df, eta
+    (eta_OS2014), the factors alpha_bar, gamma_bar, gamma_tilde, the device tensor segments [4, S] (N_s, R_s, D_s, the
+    indicator of estimate_local) and, when asked for, local [4, n] (eta_NC,T^2, r_T, eta_DF,T^2, m_T), flux [3, n],
+    oswald [n_vertices]"""
+
+    def __init__(self, sums, factors, segments, local, flux, oswald):
+        self.sums = sums
+        self.eta_nc, self.eta_r, self.eta_df = (float(np.sqrt(sums[k])) for k in range(3))
+        self.eta = float(np.sqrt(sums[3]))
+        self.alpha_bar, self.gamma_bar, self.alpha_hat, self.gamma_hat, self.gamma_tilde = factors
+        self.segments, self.local, self.flux, self.oswald = segments, local, flux, oswald
+
+    def estimate_local(self, type="eta_OS2014"):
+        """the reference's estimate_local: 3 / sqrt(alpha_bar) (sqrt(gamma_bar) N_s + R_s + gamma_tilde D_s) / eta^2 per
+        segment (device float64 [S])"""
+        if type != "eta_OS2014":
+            raise HddError("estimate_local: type is eta_OS2014")
+        return self.segments[3]
+
+
+def estimate_blocks(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=None, theta_bar=None, theta_hat=None,
+                    theta_min=None, theta_max=None, prm=None, local=False, flux=False, oswald=False, stream=None):
+    """hdd_block_swipdg_estimate: the OS2014 localized estimator of the P1 SWIPDG vector u on the segments of est
+    (Estimator.set_segments).  Arguments as estimate(); theta_min / theta_max the parameter range of the minimal
+    diffusion (None = mu).  Returns a BlockEstimate.  Synchronises the stream once."""
+    torch = _torch()
+    kappas = list(kappas)
+    n = len(kappas)
+    dev = dmesh.coords.device
+    ne = dmesh.local.n_local
+    if u.dtype != torch.float64 or u.dim() != 1 or u.numel() != 3 * ne or (u.numel() > 1 and u.stride(0) != 1):
+        raise HddError("estimate_blocks: u must be float64 [%d] with unit stride" % (3 * ne))
+    if dmesh.vertex_coords is None:
+        raise HddError("estimate_blocks: the DeviceMesh must carry its vertex-indexed geometry")
+    if est.n_segments < 1:
+        raise HddError("estimate_blocks: call Estimator.set_segments first")
+    arr = (ScalarFn * max(n, 1))(*kappas)
+    th = []
+    for t in (theta_mu, theta_bar, theta_hat, theta_min, theta_max):
+        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+        if t is not None and t.shape[0] != n:
+            raise HddError("estimate_blocks: every theta needs one entry per component")
+        th.append(t)
+    factors = os2014_factors(np.ones(n) if th[0] is None else th[0], th[1], th[2])
+    need = max(est.n_work, est.n_work_blocks, 1)
+    if est.work is None or est.work.device != dev or est.work.numel() < need:
+        est.work = torch.empty(need, dtype=torch.float64, device=dev)
+    S = est.n_segments
+    out_s = torch.empty((4, S), dtype=torch.float64, device=dev)
+    out_l = torch.empty((4, ne), dtype=torch.float64, device=dev) if local else None
+    out_f = torch.empty((3, ne), dtype=torch.float64, device=dev) if flux else None
+    out_o = torch.empty(dmesh.vertex_coords.shape[0], dtype=torch.float64, device=dev) if oswald else None
+    sums = np.zeros(4)
+    prm = prm or params_for(dmesh.local.degree, dmesh.local.dim)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _check(lib().hdd_block_swipdg_estimate(ctx.h, est.h, C.addressof(dmesh.t), arr, n, _p(th[0]), _p(th[1]), _p(th[2]),
+                                           _p(th[3]), _p(th[4]), C.addressof(tensor),
+                                           None if force is None else C.addressof(force), C.addressof(prm), u.data_ptr(),
+                                           est.work.data_ptr(), est.work.numel(), ptr(out_l), ptr(out_f), ptr(out_o),
+                                           ptr(out_s), _p(sums), C.c_void_p(s)), "hdd_block_swipdg_estimate")
+    return BlockEstimate(sums, factors, out_s, out_l, out_f, out_o)
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

@@ -759,10 +759,75 @@ int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* 
                         const hdd_tensor_fn* tensor, const hdd_scalar_fn* force, const hdd_swipdg_params* params,
                         const double* d_u, double* d_work, int64_t n_work, double* d_local, double* d_flux,
                         double* d_oswald, double* sums, void* stream);
-/* the kernels of this thread's last hdd_swipdg_estimate ("" if none), e.g.
+/* the kernels of this thread's last hdd_swipdg_estimate or hdd_block_swipdg_estimate ("" if none), e.g.
  * "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>" (beta == 1 is specialised: "pow" otherwise;
- * the force: no_force, cos_product, generic_force) */
+ * the force: no_force, cos_product, generic_force); the block call's is
+ * "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product, block> + block_segment_kernel + block_total_kernel" */
 const char* hdd_last_estimate_kernels(void);
+
+/* ---------------------------------------------------------------------------------------------- */
+/* localized estimator -- Estimators::BlockSWIPDG (estimators/block-swipdg.hh:118-328, 546-561,      */
+/* 721-890): eta_NC_OS2014, eta_R_OS2014 (eta_R_OS2014_* with hdd_estimator_set_residual_star),       */
+/* eta_DF_OS2014, eta_OS2014 and the per-subdomain indicators of estimate_local.  Additive to ABI 8.   */
+/* ---------------------------------------------------------------------------------------------- */
+/* A segment is a contiguous element range [bounds[s], bounds[s + 1]) of the estimator's whole-grid view; the view is
+ * subdomain-major, so a subdomain (or several) is a segment (hdd_grid_subdomain_range).  The segments partition [0, n).
+ * Five parameter roles: theta_mu, theta_bar, theta_hat as in hdd_swipdg_estimate, theta_min / theta_max the reference's
+ * parameter_range_min / parameter_range_max.
+ *
+ * Per element T (d_local [4][n] of the block call):
+ *   row 0  eta_NC,T^2 and row 2 eta_DF,T^2: those of hdd_swipdg_estimate, bit for bit (LocalNonconformityOS2014 and
+ *          LocalDiffusiveFluxOS2014 are the ESV2007 classes), as are d_flux and d_oswald
+ *   row 1  r_T = int_T (f - P0 f)^2 by the two simplex rules of eta_R,T^2, without its factor h_T^2 / (pi^2 lambda_min);
+ *          with residual_star on, div t_h stands for P0 f (eta_R_OS2014_*)
+ *   row 3  m_T = min(kappa_T(theta_min), kappa_T(theta_max)) lambda_min(A_T)
+ * Per segment s (d_segments [4][S]):
+ *   row 0  N_s = sum_{T in s} eta_NC,T^2          row 2  D_s = sum_{T in s} eta_DF,T^2
+ *   row 1  R_s = diam_s^2 / (pi^2 min_{T in s} m_T) sum_{T in s} r_T, diam_s the largest distance between two vertices of
+ *          the segment's elements
+ *   row 3  the indicator of estimate_local, 3 / sqrt(alpha_bar) (sqrt(gamma_bar) N_s + R_s + gamma_tilde D_s) / eta^2 with alpha_bar =
+ *          alpha(mu, mu_bar), gamma_bar = gamma(mu, mu_bar), gamma_tilde = max(sqrt(gamma(mu, mu_hat)), 1 / sqrt(alpha(mu, mu_hat)))
+ *          (block-swipdg.hh:873-887, its exponents as they stand); 0 in every segment when eta = 0 (all of N_s, R_s, D_s
+ *          vanish: e.g. u_h = 0 without a force), where the reference divides 0 by 0
+ * Global (sums [4], host): sum_s N_s, sum_s R_s, sum_s D_s and eta^2, eta_OS2014 = 1 / sqrt(alpha_bar) (sqrt(gamma_bar) eta_NC +
+ * eta_R + gamma_tilde eta_DF) with eta_NC = sqrt(sums[0]), eta_R = sqrt(sums[1]), eta_DF = sqrt(sums[2]).
+ * alpha(mu, mu') = min_q theta_q(mu) / theta_q(mu'), gamma(mu, mu') = max_q of the same ratio: the definition of the
+ * OS2014 paper for an affinely decomposed diffusion factor with non-negative components (the reference takes both from
+ * dune-pymor).  The reference asserts that they are positive: a non-positive theta in any role is HDD_ERR_INVALID.
+ *
+ * Sums, in a fixed order and without atomics, bit-identical from call to call: a segment's sum is the two-stage sum of
+ * hdd_swipdg_estimate applied to its slice -- chunks of 256 elements counted from the segment's first element, the tree
+ * v[t] += v[t + s], s = 128 .. 1, per chunk, then lane t adds the chunk sums t, t + 256, ... in order and the same tree
+ * follows -- so it does not depend on how the rest of [0, n) is cut, and with the one segment [0, n) rows 0 and 2 are
+ * sums[0] and sums[2] of hdd_swipdg_estimate.  The totals: lane t adds the segments s = t, t + 256, ... in order, then the
+ * tree.  Four launches whatever S: a lane per vertex, a lane per element over segment-aligned chunks, a workgroup per
+ * segment over its chunk sums, one workgroup for the totals, eta^2 and the scaling of the indicators. */
+/* bounds: host [n_segments + 1], strictly ascending, bounds[0] == 0, bounds[n_segments] == n (HDD_ERR_INVALID
+ * otherwise, with the tables of the last valid call kept).  Builds the per-segment host and device tables (bounds,
+ * chunk prefix, diameters: 24 B per segment); the diameters by the convex hull of the segment's distinct vertices,
+ * O(V log V), from the host geometry every estimator keeps since its creation (12 B per element, 16 B per vertex).  Allocates, so that the block call does not.  Works on a host-only estimator (no device tables).
+ * n_segments == 0 clears the tables (bounds may be NULL). */
+int hdd_estimator_set_segments(hdd_estimator* est, int64_t n_segments, const int64_t* bounds);
+/* out: host [n_segments], diam_s; HDD_ERR_INVALID without segments */
+int hdd_estimator_segment_diameters(const hdd_estimator* est, double* out);
+/* doubles of caller workspace hdd_block_swipdg_estimate needs with the segments set now: the Oswald values, four
+ * partials per chunk, the totals, four values per segment; 0 for a null estimator or without segments */
+int64_t hdd_estimator_blocks_workspace(const hdd_estimator* est);
+/* out = alpha(mu, mu_bar), gamma(mu, mu_bar), alpha(mu, mu_hat), gamma(mu, mu_hat), max(sqrt(gamma(mu, mu_hat)),
+ * 1 / sqrt(alpha(mu, mu_hat))); host [n_comp] each, theta_mu NULL: all ones, theta_bar / theta_hat NULL: theta_mu.  Pure
+ * host function.  HDD_ERR_INVALID for n_comp outside 1..HDD_MAX_COMP or a non-positive component. */
+int hdd_os2014_factors(int32_t n_comp, const double* theta_mu, const double* theta_bar, const double* theta_hat,
+                       double out[5]);
+/* The arguments, scope and checks of hdd_swipdg_estimate (every check before the first device call), and: theta_min /
+ * theta_max host [n_comp], NULL: theta_mu; d_work of n_work >= hdd_estimator_blocks_workspace doubles; d_segments NULL or
+ * device [4][n_segments].  The indicators are scaled on the device: the four sums alone cross to the host, behind the one
+ * synchronisation of `stream`.  Additionally HDD_ERR_INVALID without segments and for a non-positive theta. */
+int hdd_block_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const hdd_mesh* mesh, const hdd_scalar_fn* kappa,
+                              int32_t n_comp, const double* theta_mu, const double* theta_bar, const double* theta_hat,
+                              const double* theta_min, const double* theta_max, const hdd_tensor_fn* tensor,
+                              const hdd_scalar_fn* force, const hdd_swipdg_params* params, const double* d_u,
+                              double* d_work, int64_t n_work, double* d_local, double* d_flux, double* d_oswald,
+                              double* d_segments, double* sums, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* sharded BlockSWIPDG (SURVEY.md 8(b) hdd_block_assemble_sharded, 8(e)): one process (or thread) per  */

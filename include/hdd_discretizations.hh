@@ -1327,41 +1327,13 @@ class SWIPDG {
   Estimate estimate_all(const std::vector<double>& u, double mu, double mu_bar, double mu_hat, bool residual_star = false,
                         bool local = false) const
   {
-    assert_everything_is_ready();
-    if (!estimator_in_scope())
-      throw NotImplemented("The ESV2007 estimator needs the whole 2d conforming simplex grid with Dirichlet data on "
-                           "every boundary face!");
-    if (problem_.force.parametric()) throw NotImplemented("Not implemented for parametric force!");
-    if (int64_t(u.size()) != pattern_->rows) throw Stuff::Exceptions::wrong_input_given("estimate: vector of wrong size");
-    if (!estimator_) {
-      hdd_estimator* est = nullptr;
-      internal::check(hdd_estimator_create(ctx_, local_, &est), "hdd_estimator_create");
-      estimator_ = std::shared_ptr<hdd_estimator>(est, hdd_estimator_destroy);
-      estimator_work_ = internal::DeviceArray<double>(size_t(hdd_estimator_workspace(est)) + 1);
-    }
-    const auto& K = problem_.diffusion_factor;
-    std::vector<detail::DeviceFn> fns;
-    std::vector<double> th[3];
-    if (K.has_affine_part) {
-      fns.emplace_back(K.affine_part, view_);
-      for (auto& t : th) t.push_back(1.0);
-    }
-    for (int q = 0; q < K.num_components(); ++q) {
-      fns.emplace_back(K.components[size_t(q)], view_);
-      th[0].push_back(K.coefficients[size_t(q)].evaluate(mu));
-      th[1].push_back(K.coefficients[size_t(q)].evaluate(mu_bar));
-      th[2].push_back(K.coefficients[size_t(q)].evaluate(mu_hat));
-    }
-    std::vector<hdd_scalar_fn> kappa;
-    for (const auto& f : fns) kappa.push_back(f.fn);
-    detail::DeviceFn force;
-    const bool has_force = problem_.force.has_affine_part && !problem_.force.affine_part.is_zero();
-    if (has_force) force = detail::DeviceFn(problem_.force.affine_part, view_);
+    const EstimatorOperands o = estimator_operands(u, {mu, mu_bar, mu_hat});
     internal::DeviceArray<double> d_u(u), d_local(local ? size_t(4 * linfo_.n_local) : 0);
     Estimate out;
     internal::check(hdd_estimator_set_residual_star(estimator_.get(), residual_star), "hdd_estimator_set_residual_star");
-    internal::check(hdd_swipdg_estimate(ctx_, estimator_.get(), &mesh_, kappa.data(), int32_t(kappa.size()), th[0].data(),
-                                        th[1].data(), th[2].data(), &tensor_.fn, has_force ? &force.fn : nullptr, &prm_,
+    internal::check(hdd_swipdg_estimate(ctx_, estimator_.get(), &mesh_, o.kappa.data(), int32_t(o.kappa.size()),
+                                        o.theta[0].data(), o.theta[1].data(), o.theta[2].data(), &tensor_.fn,
+                                        o.has_force ? &o.force.fn : nullptr, &prm_,
                                         d_u.get(), estimator_work_.get(), int64_t(estimator_work_.size()),
                                         local ? d_local.get() : nullptr, nullptr, nullptr, out.sums, nullptr),
                     "hdd_swipdg_estimate");
@@ -1420,6 +1392,46 @@ class SWIPDG {
   {
     if (!initialized_)
       throw Stuff::Exceptions::you_are_using_this_wrong("The user has to call init() before calling any other method!");
+  }
+
+  // what both estimate calls hand to the library: the components of the diffusion factor with their coefficients at
+  // every parameter of `mus` (theta[role][component]) and the force; builds the estimator on the first call
+  struct EstimatorOperands {
+    std::vector<detail::DeviceFn> fns;
+    std::vector<hdd_scalar_fn> kappa;
+    std::vector<std::vector<double>> theta;
+    detail::DeviceFn force;
+    bool has_force = false;
+  };
+  EstimatorOperands estimator_operands(const std::vector<double>& u, const std::vector<double>& mus) const
+  {
+    assert_everything_is_ready();
+    if (!estimator_in_scope())
+      throw NotImplemented("The ESV2007 estimator needs the whole 2d conforming simplex grid with Dirichlet data on "
+                           "every boundary face!");
+    if (problem_.force.parametric()) throw NotImplemented("Not implemented for parametric force!");
+    if (int64_t(u.size()) != pattern_->rows) throw Stuff::Exceptions::wrong_input_given("estimate: vector of wrong size");
+    if (!estimator_) {
+      hdd_estimator* est = nullptr;
+      internal::check(hdd_estimator_create(ctx_, local_, &est), "hdd_estimator_create");
+      estimator_ = std::shared_ptr<hdd_estimator>(est, hdd_estimator_destroy);
+      estimator_work_ = internal::DeviceArray<double>(size_t(hdd_estimator_workspace(est)) + 1);
+    }
+    const auto& K = problem_.diffusion_factor;
+    EstimatorOperands o;
+    o.theta.resize(mus.size());
+    if (K.has_affine_part) {
+      o.fns.emplace_back(K.affine_part, view_);
+      for (auto& t : o.theta) t.push_back(1.0);
+    }
+    for (int q = 0; q < K.num_components(); ++q) {
+      o.fns.emplace_back(K.components[size_t(q)], view_);
+      for (size_t r = 0; r < mus.size(); ++r) o.theta[r].push_back(K.coefficients[size_t(q)].evaluate(mus[r]));
+    }
+    for (const auto& f : o.fns) o.kappa.push_back(f.fn);
+    o.has_force = problem_.force.has_affine_part && !problem_.force.affine_part.is_zero();
+    if (o.has_force) o.force = detail::DeviceFn(problem_.force.affine_part, view_);
+    return o;
   }
 
   // what hdd_swipdg_estimate covers, with the boundary info of this discretization applied
@@ -2104,6 +2116,92 @@ class BlockSWIPDG : public SWIPDG {
     return out;
   }
 
+  // Estimators::BlockSWIPDG (estimators/block-swipdg.hh:721-890): the OS2014 localized estimator, one segment per
+  // subdomain, on the device (hdd_block_swipdg_estimate).  Available where SWIPDG's estimators are.  The starred
+  // diffusive-flux variants (eta_DF_OS2014_*, eta_OS2014_*) are not covered.
+  struct BlockEstimate {
+    double sums[4] = {0.0, 0.0, 0.0, 0.0};   // sum_s N_s, sum_s R_s, sum_s D_s, eta_OS2014^2
+    std::vector<double> indicators;           // [num_subdomains()] when asked for
+    double eta_nc() const { return std::sqrt(sums[0]); }
+    double eta_r() const { return std::sqrt(sums[1]); }
+    double eta_df() const { return std::sqrt(sums[2]); }
+    double eta() const { return std::sqrt(sums[3]); }
+  };
+  std::vector<std::string> available_block_estimators() const
+  {
+    if (!estimator_in_scope()) return {};
+    return {"eta_NC_OS2014", "eta_R_OS2014", "eta_R_OS2014_*", "eta_DF_OS2014", "eta_OS2014"};
+  }
+  std::vector<std::string> available_local_block_estimators() const
+  {
+    if (!estimator_in_scope()) return {};
+    return {"eta_OS2014"};
+  }
+  // the four sums (and the indicators) of u at the reference's "mu", "mu_bar", "mu_hat", "parameter_range_min" and
+  // "parameter_range_max"; residual_star: eta_R_OS2014_* in place of eta_R_OS2014
+  BlockEstimate estimate_block_all(const std::vector<double>& u, double mu, double mu_bar, double mu_hat, double mu_min,
+                                   double mu_max, bool residual_star = false, bool indicators = false) const
+  {
+    const EstimatorOperands o = estimator_operands(u, {mu, mu_bar, mu_hat, mu_min, mu_max});
+    if (!block_segments_set_) {
+      std::vector<int64_t> bounds(size_t(num_subdomains()) + 1, 0);
+      for (int ss = 0; ss < num_subdomains(); ++ss) {
+        int64_t a;
+        internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &bounds[size_t(ss) + 1]), "hdd_grid_subdomain_range");
+      }
+      internal::check(hdd_estimator_set_segments(estimator_.get(), num_subdomains(), bounds.data()),
+                      "hdd_estimator_set_segments");
+      block_estimator_work_ = internal::DeviceArray<double>(size_t(hdd_estimator_blocks_workspace(estimator_.get())) + 1);
+      block_segments_set_ = true;
+    }
+    const size_t S = size_t(num_subdomains());
+    internal::DeviceArray<double> d_u(u), d_segments(indicators ? 4 * S : 0);
+    BlockEstimate out;
+    internal::check(hdd_estimator_set_residual_star(estimator_.get(), residual_star), "hdd_estimator_set_residual_star");
+    internal::check(hdd_block_swipdg_estimate(ctx_, estimator_.get(), &mesh_, o.kappa.data(), int32_t(o.kappa.size()),
+                                              o.theta[0].data(), o.theta[1].data(), o.theta[2].data(), o.theta[3].data(),
+                                              o.theta[4].data(), &tensor_.fn, o.has_force ? &o.force.fn : nullptr, &prm_,
+                                              d_u.get(), block_estimator_work_.get(), int64_t(block_estimator_work_.size()),
+                                              nullptr, nullptr, nullptr, indicators ? d_segments.get() : nullptr, out.sums,
+                                              nullptr),
+                    "hdd_block_swipdg_estimate");
+    if (indicators) {   // row 3 of [4][S] alone
+      out.indicators.resize(S);
+      internal::hip_check(hipMemcpy(out.indicators.data(), d_segments.get() + 3 * S, S * sizeof(double),
+                                    hipMemcpyDeviceToHost), "D2H");
+    }
+    return out;
+  }
+  // Estimators::BlockSWIPDG::estimate(space, vector, problem, type, parameters): one of available_block_estimators()
+  double estimate_block(const std::vector<double>& u, const std::string& type, double mu = 0.0) const
+  {
+    return estimate_block(u, type, mu, mu, mu, mu, mu);
+  }
+  double estimate_block(const std::vector<double>& u, const std::string& type, double mu, double mu_bar, double mu_hat,
+                        double mu_min, double mu_max) const
+  {
+    const auto ids = available_block_estimators();
+    if (!ids.empty() && std::find(ids.begin(), ids.end(), type) == ids.end())
+      throw Stuff::Exceptions::you_are_using_this_wrong("Requested type '" + type + "' is not one of available()!");
+    const BlockEstimate e = estimate_block_all(u, mu, mu_bar, mu_hat, mu_min, mu_max, type == "eta_R_OS2014_*");
+    if (type == "eta_NC_OS2014") return e.eta_nc();
+    if (type == "eta_R_OS2014" || type == "eta_R_OS2014_*") return e.eta_r();
+    return type == "eta_DF_OS2014" ? e.eta_df() : e.eta();
+  }
+  // Estimators::BlockSWIPDG::estimate_local: one indicator per subdomain -- what the online enrichment marks by
+  std::vector<double> estimate_local_block(const std::vector<double>& u, const std::string& type, double mu = 0.0) const
+  {
+    return estimate_local_block(u, type, mu, mu, mu, mu, mu);
+  }
+  std::vector<double> estimate_local_block(const std::vector<double>& u, const std::string& type, double mu, double mu_bar,
+                                           double mu_hat, double mu_min, double mu_max) const
+  {
+    const auto ids = available_local_block_estimators();
+    if (!ids.empty() && std::find(ids.begin(), ids.end(), type) == ids.end())
+      throw Stuff::Exceptions::you_are_using_this_wrong("Requested type '" + type + "' is not one of available_local()!");
+    return estimate_block_all(u, mu, mu_bar, mu_hat, mu_min, mu_max, false, true).indicators;
+  }
+
  private:
   void setup()
   {
@@ -2241,6 +2339,8 @@ class BlockSWIPDG : public SWIPDG {
   mutable std::map<std::pair<int, int>, AffinelyDecomposedMatrix> operators_;   // extract_operators()
   mutable std::vector<std::shared_ptr<SWIPDG>> local_discretizations_;
   mutable std::map<std::pair<int, std::string>, std::shared_ptr<SWIPDG>> oversampled_;
+  mutable bool block_segments_set_ = false;                       // the subdomains are the estimator's segments
+  mutable internal::DeviceArray<double> block_estimator_work_;   // built by the first estimate_block
 };
 
 // ------------------------------------------------------------------------------------------------

@@ -13,6 +13,10 @@ Algorithmic bytes (what must cross HBM once; the neighbours' data and the shared
   per element  12 elem_vertices + 12 neighbours + 4 face_info + 24 u + 8 n_per (per-element coefficient rows)
                + 12 patch DoFs + 24 u again (the vertex kernel)            [+ 32 local + 24 flux when written]
   per vertex   16 coordinates + 8 + 8 Oswald value written and read + 8 patch pointer + 1 boundary flag
+--blocks PX,PY [PX,PY ...] adds the OS2014 block call (hdd_block_swipdg_estimate), one segment per subdomain, on the same
+mesh partitioned into PX x PY subdomains (subdomain-major numbering), beside the ESV2007 call on that very mesh in the
+same alternating rounds, with and without the force; one result per partitioning under "blocks", with the time of the
+host table build (Estimator.set_segments) and the ratios block / ESV2007.
 --host also times the path a user had before: the device-to-host copy of u and the numpy restatement
 (tests/estimator_ref.py) on the same mesh, once.
 Prints one JSON line; --out DIR also writes it to DIR/bench_estimate.json."""
@@ -35,14 +39,32 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--host", action="store_true", help="also time the host path (copy of u + numpy restatement)")
+    ap.add_argument("--blocks", nargs="*", default=[], metavar="PX,PY", help="also measure the block call on PX x PY subdomains")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
     import hdd_amd as H
     torch.cuda.set_device(0)
     ctx = H.Context(0)
+    res = measure(args, H, torch, ctx, 1, 1, False)
+    if args.blocks:
+        res["blocks"] = {}
+    for spec in args.blocks:
+        px, py = (int(v) for v in spec.split(","))
+        res["blocks"]["%dx%d" % (px, py)] = measure(args, H, torch, ctx, px, py, True)
+    line = json.dumps(res)
+    print(line, flush=True)
+    if args.out:
+        os.makedirs(args.out, exist_ok=True)
+        with open(os.path.join(args.out, "bench_estimate.json"), "w") as f:
+            f.write(line + "\n")
+    return 0
+
+
+def measure(args, H, torch, ctx, px, py, blocks):
+    """the variants on the mesh partitioned into px x py subdomains; blocks: the block call beside the ESV2007 call"""
     nx, ny = args.nx, max(args.nx // 5, 1)
-    grid = H.Grid.structured(H.SIMPLEX, nx, ny, (0, 0), (5, 1))
+    grid = H.Grid.structured(H.SIMPLEX, nx, ny, (0, 0), (5, 1), px=px, py=py)
     loc = grid.local()
     k = loc.checkerboard((0, 0), (5, 1), 100, 20, 10.0 ** np.random.default_rng(10).uniform(-3, 3, 2000))
     dm = H.DeviceMesh(loc)
@@ -60,36 +82,56 @@ def main():
         "sums_local_flux": dict(kw=dict(force=force, local=True, flux=True), bytes=base + ne * (32 + 24)),
         "sums_no_force": dict(kw=dict(), bytes=base),
     }
+    set_segments_s = None
+    if blocks:
+        t0 = time.perf_counter()
+        est.set_segments(subdomains=(0, px * py))
+        set_segments_s = time.perf_counter() - t0
+        del variants["sums_local_flux"]
+        # the block call: no h_T, two more kappa roles, 4 partials per chunk and 4 values per segment in place of 4 per 256
+        variants["blocks"] = dict(kw=dict(force=force), bytes=base, call=H.estimate_blocks)
+        variants["blocks_no_force"] = dict(kw=dict(), bytes=base, call=H.estimate_blocks)
     for v in variants.values():
         v["wall_ms"], v["dev_ms"] = [], []
-    sums = None
+    sums, kernels = {}, {}
     for r in range(args.rounds):
         for key, v in variants.items():
+            call = v.get("call", H.estimate)
             for _ in range(args.warmup if r == 0 else 1):
-                e = H.estimate(ctx, est, dm, kappas, tensor, u, **v["kw"])
+                e = call(ctx, est, dm, kappas, tensor, u, **v["kw"])
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record()
             for _ in range(args.reps):
-                e = H.estimate(ctx, est, dm, kappas, tensor, u, **v["kw"])
+                e = call(ctx, est, dm, kappas, tensor, u, **v["kw"])
             e1.record()
             torch.cuda.synchronize()
             v["wall_ms"].append((time.perf_counter() - t0) * 1e3 / args.reps)
             v["dev_ms"].append(e0.elapsed_time(e1) / args.reps)
             if "force" in v["kw"]:
-                if sums is not None and not np.array_equal(sums, e.sums):
-                    raise SystemExit("sums differ between calls: %r %r" % (sums, e.sums))
-                sums = e.sums.copy()
-                kernels = H.last_estimate_kernels()
-    res = dict(config="c2_spe10_p1_%dx%d" % (nx, ny), n_elements=ne, n_vertices=nv, kernels=kernels,
-               rounds=args.rounds, reps=args.reps, estimator_create_s=create_s, sums=[float(s) for s in sums], variants={})
+                if key in sums and not np.array_equal(sums[key], e.sums):
+                    raise SystemExit("sums differ between calls: %r %r" % (sums[key], e.sums))
+                sums[key] = e.sums.copy()
+                kernels[key] = H.last_estimate_kernels()
+    res = dict(config="c2_spe10_p1_%dx%d" % (nx, ny), n_elements=ne, n_vertices=nv, kernels=kernels["sums"],
+               rounds=args.rounds, reps=args.reps, estimator_create_s=create_s, sums=[float(s) for s in sums["sums"]],
+               variants={})
+    if blocks:
+        res.update(subdomains=[px, py], set_segments_s=set_segments_s, block_kernels=kernels["blocks"],
+                   block_sums=[float(s) for s in sums["blocks"]])
     for key, v in variants.items():
         ms = float(np.median(v["wall_ms"]))
         res["variants"][key] = dict(ms=ms, ms_min=float(min(v["wall_ms"])), ms_max=float(max(v["wall_ms"])),
                                     device_ms=float(np.median(v["dev_ms"])), alg_bytes=v["bytes"],
                                     alg_TBps=v["bytes"] / ms / 1e9)
-    if args.host:
+    if blocks:
+        res["ratio_blocks_over_sums"] = res["variants"]["blocks"]["ms"] / res["variants"]["sums"]["ms"]
+        res["ratio_blocks_over_sums_no_force"] = (res["variants"]["blocks_no_force"]["ms"] /
+                                                  res["variants"]["sums_no_force"]["ms"])
+        if sums["blocks"][0] <= 0 or abs(sums["blocks"][0] - sums["sums"][0]) > 1e-12 * sums["sums"][0]:
+            raise SystemExit("sum of eta_NC^2 of the block call is not the ESV2007 call's")
+    if args.host and not blocks:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import estimator_ref as R
         ev, xy = loc.vertices()
@@ -101,14 +143,8 @@ def main():
                          force=R.esv2007_force())
         host_s = time.perf_counter() - t0
         res["host"] = dict(copy_u_ms=copy_s * 1e3, estimator_ref_ms=host_s * 1e3,
-                           rel_diff_of_sums=[float(abs(a - b) / abs(b)) for a, b in zip(sums, ref["sums"])])
-    line = json.dumps(res)
-    print(line, flush=True)
-    if args.out:
-        os.makedirs(args.out, exist_ok=True)
-        with open(os.path.join(args.out, "bench_estimate.json"), "w") as f:
-            f.write(line + "\n")
-    return 0
+                           rel_diff_of_sums=[float(abs(a - b) / abs(b)) for a, b in zip(sums["sums"], ref["sums"])])
+    return res
 
 
 if __name__ == "__main__":
