@@ -7,6 +7,7 @@
 #include <cmath>
 #include <cstdint>
 #include <new>
+#include <string>
 
 #include "abi_common.hh"
 #include "estimate_kernels.hh"
@@ -55,16 +56,18 @@ const char*& last_estimate_kernels_slot()
   return names;
 }
 
-// doubles of the workspace: Oswald values, the partial sums of the four quantities, their totals (16-byte aligned parts)
+// doubles of the workspace: Oswald values (what follows them begins at oswald_doubles: 16-byte aligned), the partial
+// sums of the four quantities, their totals
+int64_t oswald_doubles(int64_t n_vertices) { return (n_vertices + 1) & ~int64_t(1); }
 int64_t workspace_doubles(int64_t n_local, int64_t n_vertices)
 {
-  return ((n_vertices + 1) & ~int64_t(1)) + 4 * dev::estimate_workgroups(n_local) + 4;
+  return oswald_doubles(n_vertices) + 4 * dev::estimate_workgroups(n_local) + 4;
 }
 
 // the block call's: Oswald values, [4][n_chunks] partials, the four totals, [4][S] segment values
 int64_t blocks_workspace_doubles(const hdd_estimator* est)
 {
-  return ((est->n_vertices + 1) & ~int64_t(1)) + 4 * est->n_chunks + 4 + 4 * est->n_segments;
+  return oswald_doubles(est->n_vertices) + 4 * est->n_chunks + 4 + 4 * est->n_segments;
 }
 
 // theta of a role on the host: NULL -> fallback (NULL: all ones)
@@ -234,12 +237,22 @@ int check_and_fill(const char* who, hdd_ctx* ctx, const hdd_estimator* est, cons
   return HDD_OK;
 }
 
-// the launches are over: the four totals come back through the context's pinned bytes (one synchronisation)
-int fetch_sums(const char* where, hdd_ctx* ctx, const dev::EstimateArgs& a, hipStream_t s, double* sums)
+// the end of both estimate calls, a filled: the checks that need the device tables, the launches (block: the OS2014
+// call's), then the four totals come back through the context's pinned bytes (one synchronisation)
+int launch_and_fetch(const char* who, hdd_ctx* ctx, const hdd_estimator* est, const dev::EstimateArgs& a, bool block, void* stream, double* sums)
 {
-  hipError_t e = hipMemcpyAsync(ctx->solve_state_h, a.total, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
+  auto at = [who](const char* step) { return std::string(who) + step; };
+  if (!est->patch_ptr || (block && !est->seg_tab))
+    return fail(HDD_ERR_INVALID, who, "host-only estimator (created without a context)");
+  if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
+  hipError_t e = hipSetDevice(ctx->device);
+  if (e != hipSuccess) return hip_fail(e, at(": hipSetDevice").c_str());
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  e = block ? dev::launch_estimate_blocks(a, s, &last_estimate_kernels_slot()) : dev::launch_estimate(a, s, &last_estimate_kernels_slot());
+  if (e != hipSuccess) return hip_fail(e, at(": launch").c_str());
+  e = hipMemcpyAsync(ctx->solve_state_h, a.total, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
   if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return hip_fail(e, where);
+  if (e != hipSuccess) return hip_fail(e, at(": sums").c_str());
   for (int r = 0; r < 4; ++r) sums[r] = ctx->solve_state_h[r];
   return HDD_OK;
 }
@@ -257,16 +270,9 @@ extern "C" int hdd_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est, const
                               n_work, est ? workspace_doubles(est->n_local, est->n_vertices) : 0,
                               "n_work below hdd_estimator_workspace", d_local, d_flux, d_oswald, sums, a))
     return rc;
-  a.partial = d_work + ((est->n_vertices + 1) & ~int64_t(1));
+  a.partial = d_work + oswald_doubles(est->n_vertices);
   a.total = a.partial + 4 * dev::estimate_workgroups(a.n);
-  if (!est->patch_ptr) return fail(HDD_ERR_INVALID, who, "host-only estimator (created without a context)");
-  if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return hip_fail(e, "hdd_swipdg_estimate: hipSetDevice");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  e = dev::launch_estimate(a, s, &last_estimate_kernels_slot());
-  if (e != hipSuccess) return hip_fail(e, "hdd_swipdg_estimate: launch");
-  return fetch_sums("hdd_swipdg_estimate: sums", ctx, a, s, sums);
+  return launch_and_fetch(who, ctx, est, a, false, stream, sums);
 }
 
 extern "C" int hdd_estimator_set_segments(hdd_estimator* est, int64_t n_segments, const int64_t* bounds)
@@ -373,16 +379,8 @@ extern "C" int hdd_block_swipdg_estimate(hdd_ctx* ctx, const hdd_estimator* est,
   a.seg_bounds = est->seg_tab;
   a.chunk_prefix = est->seg_tab + (S + 1);
   a.seg_diam = est->seg_diam;
-  a.partial = d_work + ((est->n_vertices + 1) & ~int64_t(1));
+  a.partial = d_work + oswald_doubles(est->n_vertices);
   a.total = a.partial + 4 * a.n_chunks;
   a.segments = d_segments ? d_segments : a.total + 4;
-  if (!est->patch_ptr || !est->seg_tab)
-    return fail(HDD_ERR_INVALID, who, "host-only estimator (created without a context)");
-  if (!ctx->solve_state_h) return fail(HDD_ERR_INVALID, who, "context without its state buffer");
-  hipError_t e = hipSetDevice(ctx->device);
-  if (e != hipSuccess) return hip_fail(e, "hdd_block_swipdg_estimate: hipSetDevice");
-  const hipStream_t s = static_cast<hipStream_t>(stream);
-  e = dev::launch_estimate_blocks(a, s, &last_estimate_kernels_slot());
-  if (e != hipSuccess) return hip_fail(e, "hdd_block_swipdg_estimate: launch");
-  return fetch_sums("hdd_block_swipdg_estimate: sums", ctx, a, s, sums);
+  return launch_and_fetch(who, ctx, est, a, true, stream, sums);
 }

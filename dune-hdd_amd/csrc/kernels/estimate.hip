@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <string>
+#include <type_traits>
 
 #include "elem_affine.hh"
 #include "estimate_kernels.hh"
@@ -341,47 +343,43 @@ __global__ void __launch_bounds__(ESTIMATE_WG) estimate_sum_kernel(const double*
   if (t < 4) total[t] = sh[t][0];
 }
 
-template <bool BETA1, int FORCE, bool BLOCK = false>
+template <bool BETA1, int FORCE, bool BLOCK>
 hipError_t launch_element(const EstimateArgs& a, unsigned n_wg, hipStream_t s)
 {
   hipLaunchKernelGGL((esv2007_element_kernel<BETA1, FORCE, BLOCK>), dim3(n_wg), dim3(ESTIMATE_WG), 0, s, a);
   return hipGetLastError();
 }
 
-hipError_t launch_oswald(const EstimateArgs& a, hipStream_t s)
+// the Oswald launch, then the element kernel of (a.beta_is_one, the kind of force, block) on n_wg workgroups; *names:
+// the instantiations of the whole call
+hipError_t launch_oswald_and_elements(const EstimateArgs& a, bool block, unsigned n_wg, hipStream_t s, const char** names)
 {
   const int64_t v_wg = (a.n_vertices + ESTIMATE_WG - 1) / ESTIMATE_WG;
-  if (v_wg <= 0) return hipSuccess;
-  hipLaunchKernelGGL(oswald_vertex_kernel, dim3(unsigned(v_wg)), dim3(ESTIMATE_WG), 0, s, a.n_vertices, a.patch_ptr,
-                     a.patch_dof, a.vertex_bnd, a.u, a.oswald, a.out_oswald);
-  return hipGetLastError();
+  if (v_wg > 0) {
+    hipLaunchKernelGGL(oswald_vertex_kernel, dim3(unsigned(v_wg)), dim3(ESTIMATE_WG), 0, s, a.n_vertices, a.patch_ptr, a.patch_dof,
+                       a.vertex_bnd, a.u, a.oswald, a.out_oswald);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
+  static const char* const forces[3] = {"no_force", "cos_product", "generic_force"};
+  thread_local std::string nm;
+  nm = std::string("oswald_vertex_kernel + esv2007_element_kernel<") + (a.beta_is_one ? "beta1, " : "pow, ") + forces[force] +
+       (block ? ", block> + block_segment_kernel + block_total_kernel" : ">");
+  *names = nm.c_str();
+  auto of_force = [&](auto BETA1, auto BLOCK) {
+    return force == 0 ? launch_element<BETA1(), 0, BLOCK()>(a, n_wg, s)
+                      : (force == 1 ? launch_element<BETA1(), 1, BLOCK()>(a, n_wg, s) : launch_element<BETA1(), 2, BLOCK()>(a, n_wg, s));
+  };
+  auto of_beta = [&](auto BLOCK) { return a.beta_is_one ? of_force(std::true_type{}, BLOCK) : of_force(std::false_type{}, BLOCK); };
+  return block ? of_beta(std::true_type{}) : of_beta(std::false_type{});
 }
 
 }  // namespace
 
 hipError_t launch_estimate_blocks(const EstimateArgs& a, hipStream_t s, const char** names)
 {
-  hipError_t e = launch_oswald(a, s);
-  if (e != hipSuccess) return e;
-  const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
-  const unsigned n_wg = unsigned(a.n_chunks);
-  static const char* nm[2][3] = {
-      {"oswald_vertex_kernel + esv2007_element_kernel<pow, no_force, block> + block_segment_kernel + block_total_kernel",
-       "oswald_vertex_kernel + esv2007_element_kernel<pow, cos_product, block> + block_segment_kernel + block_total_kernel",
-       "oswald_vertex_kernel + esv2007_element_kernel<pow, generic_force, block> + block_segment_kernel + "
-       "block_total_kernel"},
-      {"oswald_vertex_kernel + esv2007_element_kernel<beta1, no_force, block> + block_segment_kernel + block_total_kernel",
-       "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product, block> + block_segment_kernel + "
-       "block_total_kernel",
-       "oswald_vertex_kernel + esv2007_element_kernel<beta1, generic_force, block> + block_segment_kernel + "
-       "block_total_kernel"}};
-  *names = nm[a.beta_is_one ? 1 : 0][force];
-  if (a.beta_is_one)
-    e = force == 0 ? launch_element<true, 0, true>(a, n_wg, s)
-                   : (force == 1 ? launch_element<true, 1, true>(a, n_wg, s) : launch_element<true, 2, true>(a, n_wg, s));
-  else
-    e = force == 0 ? launch_element<false, 0, true>(a, n_wg, s)
-                   : (force == 1 ? launch_element<false, 1, true>(a, n_wg, s) : launch_element<false, 2, true>(a, n_wg, s));
+  hipError_t e = launch_oswald_and_elements(a, true, unsigned(a.n_chunks), s, names);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(block_segment_kernel, dim3(unsigned(a.n_segments)), dim3(ESTIMATE_WG), 0, s, a);
   e = hipGetLastError();
@@ -393,24 +391,7 @@ hipError_t launch_estimate_blocks(const EstimateArgs& a, hipStream_t s, const ch
 hipError_t launch_estimate(const EstimateArgs& a, hipStream_t s, const char** names)
 {
   const int64_t n_wg = estimate_workgroups(a.n);
-  hipError_t e = launch_oswald(a, s);
-  if (e != hipSuccess) return e;
-  const int force = !a.has_force ? 0 : (a.force.kind == HDD_FN_COS_PRODUCT ? 1 : 2);
-  if (a.beta_is_one) {
-    static const char* nm[3] = {"oswald_vertex_kernel + esv2007_element_kernel<beta1, no_force>",
-                                "oswald_vertex_kernel + esv2007_element_kernel<beta1, cos_product>",
-                                "oswald_vertex_kernel + esv2007_element_kernel<beta1, generic_force>"};
-    *names = nm[force];
-    e = force == 0 ? launch_element<true, 0>(a, unsigned(n_wg), s)
-                   : (force == 1 ? launch_element<true, 1>(a, unsigned(n_wg), s) : launch_element<true, 2>(a, unsigned(n_wg), s));
-  } else {
-    static const char* nm[3] = {"oswald_vertex_kernel + esv2007_element_kernel<pow, no_force>",
-                                "oswald_vertex_kernel + esv2007_element_kernel<pow, cos_product>",
-                                "oswald_vertex_kernel + esv2007_element_kernel<pow, generic_force>"};
-    *names = nm[force];
-    e = force == 0 ? launch_element<false, 0>(a, unsigned(n_wg), s)
-                   : (force == 1 ? launch_element<false, 1>(a, unsigned(n_wg), s) : launch_element<false, 2>(a, unsigned(n_wg), s));
-  }
+  const hipError_t e = launch_oswald_and_elements(a, false, unsigned(n_wg), s, names);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(estimate_sum_kernel, dim3(1), dim3(ESTIMATE_WG), 0, s, a.partial, n_wg, a.total);
   return hipGetLastError();

@@ -1023,6 +1023,27 @@ def _solve_operands(batched, dpattern, vals, theta, dmesh, block, grid, B, X0, r
     return operator, (th, rng), rows, n_rhs, ldb, X, opt, C.c_void_p(s)
 
 
+def _solve_buffers(n_infos, rows, opt, workspace, history, device):
+    """the tail the solver calls share, before the ABI call: the workspace (n_work = workspace(rows, block_size,
+    n_infos) doubles), the zeroed histories [n_infos, ldh] (None unless history) and the infos for the call to fill"""
+    torch = _torch()
+    n_work = max(int(workspace(rows, opt.block_size, n_infos)), 1)
+    work = torch.empty(n_work, dtype=torch.float64, device=device)
+    ldh = max(opt.max_iter, 0) + 1
+    hist = torch.zeros((n_infos, ldh), dtype=torch.float64, device=device) if history else None
+    return work, n_work, hist, ldh, (SolveInfo * n_infos)()
+
+
+def _solve_infos(infos, hist):
+    """... and after it: the filled infos as a list of SolveInfo, each with .history (its iterations + 1 residuals)"""
+    out = []
+    for j, filled in enumerate(infos):
+        i = SolveInfo(filled.status, filled.iterations, filled.residual, filled.rhs_norm)
+        i.history = None if hist is None else hist[j, :i.iterations + 1]
+        out.append(i)
+    return out
+
+
 def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, rtol=1e-8, atol=0.0, max_iter=10000,
           precond="block_jacobi", block_size=0, check_every=0, history=False, stream=None, grid=None):
     """hdd_operator_solve: x with (sum_q theta[q] A_q) x = b by (block-)Jacobi preconditioned conjugate gradients on
@@ -1032,17 +1053,13 @@ def solve(ctx, dpattern, vals, b, theta=None, dmesh=None, block=None, x0=None, r
     pattern's LocalMesh when dmesh is None; precond="none" without either: 1).  Returns (x, info): info a SolveInfo
     (status SOLVE_*, iterations, residual, rhs_norm) that also carries .history (device [iterations + 1], ||r_k||) when
     history=True.  Synchronises the stream at every look (check_every iterations, default 32)."""
-    torch = _torch()
     operator, keep, rows, _, _, x, opt, s = _solve_operands(False, dpattern, vals, theta, dmesh, block, grid, b, x0, rtol, atol,
                                                             max_iter, precond, block_size, check_every, stream)
-    n_work = max(int(lib().hdd_operator_solve_workspace(rows, opt.block_size)), 1)
-    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
-    hist = torch.zeros(max(int(max_iter), 0) + 1, dtype=torch.float64, device=b.device) if history else None
-    info = SolveInfo()
+    work, n_work, hist, _, infos = _solve_buffers(1, rows, opt, lambda r, bs, _: lib().hdd_operator_solve_workspace(r, bs),
+                                                  history, b.device)
     _check(lib().hdd_operator_solve(ctx.h, *operator, b.data_ptr(), x.data_ptr(), C.addressof(opt), work.data_ptr(), n_work,
-                                    None if hist is None else hist.data_ptr(), C.addressof(info), s), "hdd_operator_solve")
-    info.history = None if hist is None else hist[:info.iterations + 1]
-    return x, info
+                                    None if hist is None else hist.data_ptr(), C.addressof(infos), s), "hdd_operator_solve")
+    return x, _solve_infos(infos, hist)[0]
 
 
 def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0=None, rtol=1e-8, atol=0.0,
@@ -1054,23 +1071,13 @@ def solve_batched(ctx, dpattern, vals, B, theta=None, dmesh=None, block=None, X0
     columns.  Returns (X, infos): X [n_rhs, rows], infos a list of SolveInfo (each with .history when history=True).
     Column j is bit for bit what solve() gives for (B[j], X0[j]); the value arrays and the inverse blocks are read
     once per group of four columns and iteration."""
-    torch = _torch()
     operator, keep, rows, n_rhs, ldb, X, opt, s = _solve_operands(True, dpattern, vals, theta, dmesh, block, grid, B, X0, rtol, atol,
                                                                   max_iter, precond, block_size, check_every, stream)
-    n_work = max(int(lib().hdd_operator_solve_batched_workspace(rows, opt.block_size, n_rhs)), 1)
-    work = torch.empty(n_work, dtype=torch.float64, device=B.device)
-    ldh = max(int(max_iter), 0) + 1
-    hist = torch.zeros((n_rhs, ldh), dtype=torch.float64, device=B.device) if history else None
-    infos = (SolveInfo * n_rhs)()
+    work, n_work, hist, ldh, infos = _solve_buffers(n_rhs, rows, opt, lib().hdd_operator_solve_batched_workspace, history, B.device)
     _check(lib().hdd_operator_solve_batched(ctx.h, *operator, B.data_ptr(), ldb, X.data_ptr(), max(rows, 1), n_rhs,
                                             C.addressof(opt), work.data_ptr(), n_work, None if hist is None else hist.data_ptr(),
                                             ldh, C.addressof(infos), s), "hdd_operator_solve_batched")
-    out = []
-    for j in range(n_rhs):
-        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
-        i.history = None if hist is None else hist[j, :i.iterations + 1]
-        out.append(i)
-    return X, out
+    return X, _solve_infos(infos, hist)
 
 
 def _thetas(who, thetas, n, n_comp):
@@ -1108,26 +1115,22 @@ def solve_multi(ctx, dpattern, vals, B, thetas, dmesh=None, block=None, X0=None,
     and the result (X, infos) are solve_batched()'s.  EVERY A(thetas[j]) MUST BE SYMMETRIC POSITIVE DEFINITE.  Column
     j is bit for bit solve(..., B[j], theta=thetas[j], x0=X0[j]) on the same path (apply_multi's dispatch); a diagonal
     block that is not positive definite at thetas[j] breaks column j alone down (SOLVE_BREAKDOWN, 0 iterations)."""
-    torch = _torch()
     operator, keep, rows, n_rhs, ldb, X, opt, s = _solve_operands(True, dpattern, vals, None, dmesh, block, grid, B, X0, rtol, atol,
                                                                   max_iter, precond, block_size, check_every, stream)
     n_comp = operator[3]
     th = _thetas("solve_multi", thetas, n_rhs, n_comp)
-    n_work = max(int(lib().hdd_operator_solve_multi_workspace(rows, opt.block_size, n_rhs)), 1)
-    work = torch.empty(n_work, dtype=torch.float64, device=B.device)
-    ldh = max(int(max_iter), 0) + 1
-    hist = torch.zeros((n_rhs, ldh), dtype=torch.float64, device=B.device) if history else None
-    infos = (SolveInfo * n_rhs)()
+    work, n_work, hist, ldh, infos = _solve_buffers(n_rhs, rows, opt, lib().hdd_operator_solve_multi_workspace, history, B.device)
     _check(lib().hdd_operator_solve_multi(ctx.h, *operator[:4], _p(th), n_comp, operator[5], B.data_ptr(), ldb, X.data_ptr(),
                                           max(rows, 1), n_rhs, C.addressof(opt), work.data_ptr(), n_work,
                                           None if hist is None else hist.data_ptr(), ldh, C.addressof(infos), s),
            "hdd_operator_solve_multi")
-    out = []
-    for j in range(n_rhs):
-        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
-        i.history = None if hist is None else hist[j, :i.iterations + 1]
-        out.append(i)
-    return X, out
+    return X, _solve_infos(infos, hist)
+
+
+def _subdomain_bounds(grid, subdomains, unit=1):
+    """the bounds [s1 - s0 + 1] of the subdomains s0 <= s < s1 of `grid` in elements (unit 1) or rows (unit grid.nb)"""
+    s0, s1 = subdomains
+    return [grid.subdomain_range(s0, s0 + 1)[0] * unit] + [grid.subdomain_range(s, s + 1)[1] * unit for s in range(s0, s1)]
 
 
 def _segment_bounds(who, dpattern, dmesh, bounds, subdomains, grid):
@@ -1141,8 +1144,7 @@ def _segment_bounds(who, dpattern, dmesh, bounds, subdomains, grid):
             if local is None:
                 raise HddError("%s: subdomains= needs a Grid (grid=, or a DevicePattern / DeviceMesh that has one)" % who)
             grid = local.grid
-        s0, s1 = subdomains
-        bounds = [grid.subdomain_range(s, s + 1)[0] * grid.nb for s in range(s0, s1)] + [grid.subdomain_range(s1 - 1, s1)[1] * grid.nb]
+        bounds = _subdomain_bounds(grid, subdomains, grid.nb)
     bd = np.ascontiguousarray(bounds, np.int64).reshape(-1)
     if bd.shape[0] < 2:
         raise HddError("%s: bounds needs at least two entries" % who)
@@ -1182,26 +1184,16 @@ def solve_blocks(ctx, dpattern, vals, b, theta=None, dmesh=None, bounds=None, su
     segment (each with .history when history=True).  Segment s is bit for bit solve(..., b_s, x0=x0_s,
     block=(bounds[s], bounds[s + 1], bounds[s], bounds[s + 1])) on the same path; EVERY A_ss MUST BE SYMMETRIC POSITIVE
     DEFINITE."""
-    torch = _torch()
     bd = _segment_bounds("solve_blocks", dpattern, dmesh, bounds, subdomains, grid)
     n_blocks = int(bd.shape[0]) - 1
     interval = BlockRange(int(bd[0]), int(bd[-1]), int(bd[0]), int(bd[-1]))
     operator, keep, rows, _, _, x, opt, s = _solve_operands(False, dpattern, vals, theta, dmesh, interval, grid, b, x0, rtol, atol,
                                                             max_iter, precond, block_size, check_every, stream)
-    n_work = max(int(lib().hdd_operator_solve_blocks_workspace(rows, opt.block_size, n_blocks)), 1)
-    work = torch.empty(n_work, dtype=torch.float64, device=b.device)
-    ldh = max(int(max_iter), 0) + 1
-    hist = torch.zeros((n_blocks, ldh), dtype=torch.float64, device=b.device) if history else None
-    infos = (SolveInfo * n_blocks)()
+    work, n_work, hist, ldh, infos = _solve_buffers(n_blocks, rows, opt, lib().hdd_operator_solve_blocks_workspace, history, b.device)
     _check(lib().hdd_operator_solve_blocks(ctx.h, *operator[:5], n_blocks, bd.ctypes.data, b.data_ptr(), x.data_ptr(),
                                            C.addressof(opt), work.data_ptr(), n_work, None if hist is None else hist.data_ptr(),
                                            ldh, C.addressof(infos), s), "hdd_operator_solve_blocks")
-    out = []
-    for j in range(n_blocks):
-        i = SolveInfo(infos[j].status, infos[j].iterations, infos[j].residual, infos[j].rhs_norm)
-        i.history = None if hist is None else hist[j, :i.iterations + 1]
-        out.append(i)
-    return x, out
+    return x, _solve_infos(infos, hist)
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -1232,9 +1224,7 @@ class Estimator:
         if subdomains is not None:
             if bounds is not None:
                 raise HddError("set_segments: give bounds or subdomains, not both")
-            s0, s1 = subdomains
-            bounds = [self.local.grid.subdomain_range(s0, s0 + 1)[0]]
-            bounds += [self.local.grid.subdomain_range(s, s + 1)[1] for s in range(s0, s1)]
+            bounds = _subdomain_bounds(self.local.grid, subdomains)
         if bounds is None:
             _check(lib().hdd_estimator_set_segments(self.h, 0, None), "hdd_estimator_set_segments")
             self.n_segments, self.n_work_blocks = 0, 0
@@ -1283,6 +1273,39 @@ class Estimate:
         raise HddError("estimate_local: type is eta_ESV2007 or eta_ESV2007_alt")
 
 
+def _estimate_operands(who, est, dmesh, kappas, u, thetas, need, prm, local, flux, oswald, stream):
+    """what estimate and estimate_blocks (who) share: the checks of u and dmesh, the components as the ABI's array
+    and their number, every theta role of `thetas` as a host array or None, est.work of at least `need` doubles on the
+    mesh's device, the outputs asked for (local, flux, oswald: tensors or None), the sums, the parameters, the stream"""
+    torch = _torch()
+    kappas = list(kappas)
+    n = len(kappas)
+    dev = dmesh.coords.device
+    ne = dmesh.local.n_local
+    if u.dtype != torch.float64 or u.dim() != 1 or u.numel() != 3 * ne or (u.numel() > 1 and u.stride(0) != 1):
+        raise HddError("%s: u must be float64 [%d] with unit stride" % (who, 3 * ne))
+    if dmesh.vertex_coords is None:
+        raise HddError("%s: the DeviceMesh must carry its vertex-indexed geometry" % who)
+    th = []
+    for t in thetas:
+        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
+        if t is not None and t.shape[0] != n:
+            raise HddError("%s: every theta needs one entry per component" % who)
+        th.append(t)
+    if est.work is None or est.work.device != dev or est.work.numel() < need:
+        est.work = torch.empty(need, dtype=torch.float64, device=dev)
+    outs = [torch.empty((4, ne), dtype=torch.float64, device=dev) if local else None,
+            torch.empty((3, ne), dtype=torch.float64, device=dev) if flux else None,
+            torch.empty(dmesh.vertex_coords.shape[0], dtype=torch.float64, device=dev) if oswald else None]
+    prm = prm or params_for(dmesh.local.degree, dmesh.local.dim)
+    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
+    return (ScalarFn * max(n, 1))(*kappas), n, th, outs, np.zeros(4), prm, C.c_void_p(s)
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def estimate(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=None, theta_bar=None, theta_hat=None, prm=None,
              local=False, flux=False, oswald=False, stream=None):
     """hdd_swipdg_estimate: the ESV2007 estimator of the P1 SWIPDG vector u (device float64 [3 n]) on the device.
@@ -1290,36 +1313,13 @@ def estimate(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=None, thet
     the parameters of the flux reconstruction (mu), the nonconformity (bar: None = mu) and the diffusive flux (hat:
     None = mu); force: the scalar_fn of the right-hand side or None.  Returns an Estimate; local / flux / oswald ask
     for the per-element arrays, the RT0 fluxes F_T,e and the Oswald vector.  Synchronises the stream once."""
-    torch = _torch()
-    kappas = list(kappas)
-    n = len(kappas)
-    dev = dmesh.coords.device
-    ne = dmesh.local.n_local
-    if u.dtype != torch.float64 or u.dim() != 1 or u.numel() != 3 * ne or (u.numel() > 1 and u.stride(0) != 1):
-        raise HddError("estimate: u must be float64 [%d] with unit stride" % (3 * ne))
-    if dmesh.vertex_coords is None:
-        raise HddError("estimate: the DeviceMesh must carry its vertex-indexed geometry")
-    arr = (ScalarFn * max(n, 1))(*kappas)
-    th = []
-    for t in (theta_mu, theta_bar, theta_hat):
-        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
-        if t is not None and t.shape[0] != n:
-            raise HddError("estimate: every theta needs one entry per component")
-        th.append(t)
-    if est.work is None or est.work.device != dev:
-        est.work = torch.empty(max(est.n_work, 1), dtype=torch.float64, device=dev)
-    out_l = torch.empty((4, ne), dtype=torch.float64, device=dev) if local else None
-    out_f = torch.empty((3, ne), dtype=torch.float64, device=dev) if flux else None
-    out_o = torch.empty(dmesh.vertex_coords.shape[0], dtype=torch.float64, device=dev) if oswald else None
-    sums = np.zeros(4)
-    prm = prm or params_for(dmesh.local.degree, dmesh.local.dim)
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    ptr = lambda t: None if t is None else t.data_ptr()
+    arr, n, th, outs, sums, prm, s = _estimate_operands("estimate", est, dmesh, kappas, u, (theta_mu, theta_bar, theta_hat),
+                                                       max(est.n_work, 1), prm, local, flux, oswald, stream)
     _check(lib().hdd_swipdg_estimate(ctx.h, est.h, C.addressof(dmesh.t), arr, n, _p(th[0]), _p(th[1]), _p(th[2]),
                                      C.addressof(tensor), None if force is None else C.addressof(force), C.addressof(prm),
-                                     u.data_ptr(), est.work.data_ptr(), est.n_work, ptr(out_l), ptr(out_f), ptr(out_o),
-                                     _p(sums), C.c_void_p(s)), "hdd_swipdg_estimate")
-    return Estimate(sums, out_l, out_f, out_o)
+                                     u.data_ptr(), est.work.data_ptr(), est.n_work, _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                     _p(sums), s), "hdd_swipdg_estimate")
+    return Estimate(sums, *outs)
 
 
 def os2014_factors(theta_mu, theta_bar=None, theta_hat=None):
@@ -1364,43 +1364,19 @@ def estimate_blocks(ctx, est, dmesh, kappas, tensor, u, force=None, theta_mu=Non
     """hdd_block_swipdg_estimate: the OS2014 localized estimator of the P1 SWIPDG vector u on the segments of est
     (Estimator.set_segments).  Arguments as estimate(); theta_min / theta_max the parameter range of the minimal
     diffusion (None = mu).  Returns a BlockEstimate.  Synchronises the stream once."""
-    torch = _torch()
-    kappas = list(kappas)
-    n = len(kappas)
-    dev = dmesh.coords.device
-    ne = dmesh.local.n_local
-    if u.dtype != torch.float64 or u.dim() != 1 or u.numel() != 3 * ne or (u.numel() > 1 and u.stride(0) != 1):
-        raise HddError("estimate_blocks: u must be float64 [%d] with unit stride" % (3 * ne))
-    if dmesh.vertex_coords is None:
-        raise HddError("estimate_blocks: the DeviceMesh must carry its vertex-indexed geometry")
     if est.n_segments < 1:
         raise HddError("estimate_blocks: call Estimator.set_segments first")
-    arr = (ScalarFn * max(n, 1))(*kappas)
-    th = []
-    for t in (theta_mu, theta_bar, theta_hat, theta_min, theta_max):
-        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(-1)
-        if t is not None and t.shape[0] != n:
-            raise HddError("estimate_blocks: every theta needs one entry per component")
-        th.append(t)
+    arr, n, th, outs, sums, prm, s = _estimate_operands("estimate_blocks", est, dmesh, kappas, u,
+                                                       (theta_mu, theta_bar, theta_hat, theta_min, theta_max),
+                                                       max(est.n_work, est.n_work_blocks, 1), prm, local, flux, oswald, stream)
     factors = os2014_factors(np.ones(n) if th[0] is None else th[0], th[1], th[2])
-    need = max(est.n_work, est.n_work_blocks, 1)
-    if est.work is None or est.work.device != dev or est.work.numel() < need:
-        est.work = torch.empty(need, dtype=torch.float64, device=dev)
-    S = est.n_segments
-    out_s = torch.empty((4, S), dtype=torch.float64, device=dev)
-    out_l = torch.empty((4, ne), dtype=torch.float64, device=dev) if local else None
-    out_f = torch.empty((3, ne), dtype=torch.float64, device=dev) if flux else None
-    out_o = torch.empty(dmesh.vertex_coords.shape[0], dtype=torch.float64, device=dev) if oswald else None
-    sums = np.zeros(4)
-    prm = prm or params_for(dmesh.local.degree, dmesh.local.dim)
-    s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    ptr = lambda t: None if t is None else t.data_ptr()
+    out_s = est.work.new_empty((4, est.n_segments))
     _check(lib().hdd_block_swipdg_estimate(ctx.h, est.h, C.addressof(dmesh.t), arr, n, _p(th[0]), _p(th[1]), _p(th[2]),
                                            _p(th[3]), _p(th[4]), C.addressof(tensor),
                                            None if force is None else C.addressof(force), C.addressof(prm), u.data_ptr(),
-                                           est.work.data_ptr(), est.work.numel(), ptr(out_l), ptr(out_f), ptr(out_o),
-                                           ptr(out_s), _p(sums), C.c_void_p(s)), "hdd_block_swipdg_estimate")
-    return BlockEstimate(sums, factors, out_s, out_l, out_f, out_o)
+                                           est.work.data_ptr(), est.work.numel(), _ptr(outs[0]), _ptr(outs[1]), _ptr(outs[2]),
+                                           out_s.data_ptr(), _p(sums), s), "hdd_block_swipdg_estimate")
+    return BlockEstimate(sums, factors, out_s, *outs)
 
 
 def soa_gather(ctx, arrays, rows, ld, idx, buf, stream=None):

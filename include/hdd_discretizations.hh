@@ -713,33 +713,24 @@ class AffinelyDecomposedMatrix {
   hdd_solve_info apply_inverse(const double* d_b, double* d_x, double mu = 0.0, const SolverOptions& options = SolverOptions(),
                                const hdd_block_range* range = nullptr, bool x0 = false, void* stream = nullptr) const
   {
-    std::vector<const double*> v;
-    std::vector<double> theta;
-    operands(mu, v, theta);
-    const hdd_csr pat = pattern->csr();
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
-    const hdd_solve_options opt = solve_options(options, x0);
-    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_workspace(rows, opt.block_size), 1);
-    internal::DeviceArray<double> work{size_t(n_work)};
-    hdd_solve_info info{};
-    internal::check(hdd_operator_solve(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
-                                       theta.data(), range, d_b, d_x, &opt, work.get(), n_work, nullptr, &info, stream),
-                    "hdd_operator_solve");
-    if (info.status != HDD_SOLVE_CONVERGED) throw Stuff::Exceptions::linear_solver_failed(solver_failed(info, ""));
-    return info;
+    const int64_t rows = rows_of(range);
+    return solved("hdd_operator_solve", {mu}, 1, options, x0, [&](int32_t bs) { return hdd_operator_solve_workspace(rows, bs); },
+                  [&](const SolveCall& o) {
+                    return hdd_operator_solve(ctx, o.mesh, o.pat, o.vals, o.n_comp, o.theta, range, d_b, d_x, o.opt, o.work, o.n_work,
+                                              nullptr, o.infos, stream);
+                  },
+                  [](int32_t) { return std::string(); })[0];
   }
   std::vector<double> apply_inverse(const std::vector<double>& b, double mu = 0.0, const SolverOptions& options = SolverOptions(),
                                     const hdd_block_range* range = nullptr, hdd_solve_info* info = nullptr) const
   {
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
+    const int64_t rows = rows_of(range), ld = std::max<int64_t>(rows, 1);
     if (int64_t(b.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
-    internal::DeviceArray<double> db{size_t(std::max<int64_t>(rows, 1))}, dx{size_t(std::max<int64_t>(rows, 1))};
-    if (rows) internal::hip_check(hipMemcpy(db.get(), b.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_inverse");
+    const auto db = upload_columns(1, rows, ld, "apply_inverse", [&](size_t) { return b.data(); });
+    internal::DeviceArray<double> dx{size_t(ld)};
     const hdd_solve_info i = apply_inverse(db.get(), dx.get(), mu, options, range);
     if (info) *info = i;
-    auto x = dx.download();
-    x.resize(size_t(rows));
-    return x;
+    return download_first(dx, rows);
   }
   // X = A(mu)^-1 B for n_rhs (1..HDD_MAX_VEC) right-hand sides at once (hdd_operator_solve_batched: pyMOR's
   // apply_inverse on a VectorArray): d_b [n_rhs][ldb], d_x [n_rhs][ldx] device arrays.  Column j is bit for bit what
@@ -750,47 +741,25 @@ class AffinelyDecomposedMatrix {
                                             bool x0 = false, void* stream = nullptr) const
   {
     if (n_rhs < 1 || n_rhs > HDD_MAX_VEC) throw Stuff::Exceptions::wrong_input_given("apply_inverse: n_rhs outside 1..HDD_MAX_VEC");
-    std::vector<const double*> v;
-    std::vector<double> theta;
-    operands(mu, v, theta);
-    const hdd_csr pat = pattern->csr();
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
-    const hdd_solve_options opt = solve_options(options, x0);
-    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_batched_workspace(rows, opt.block_size, n_rhs), 1);
-    internal::DeviceArray<double> work{size_t(n_work)};
-    std::vector<hdd_solve_info> infos(size_t(n_rhs), hdd_solve_info{});
-    internal::check(hdd_operator_solve_batched(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
-                                               theta.data(), range, d_b, ldb, d_x, ldx, n_rhs, &opt, work.get(), n_work,
-                                               nullptr, 0, infos.data(), stream),
-                    "hdd_operator_solve_batched");
-    for (int32_t j = 0; j < n_rhs; ++j)
-      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
-        throw Stuff::Exceptions::linear_solver_failed(
-            solver_failed(infos[size_t(j)], " for right-hand side " + std::to_string(j) + " of " + std::to_string(n_rhs)));
-    return infos;
+    const int64_t rows = rows_of(range);
+    return solved("hdd_operator_solve_batched", {mu}, n_rhs, options, x0,
+                  [&](int32_t bs) { return hdd_operator_solve_batched_workspace(rows, bs, n_rhs); },
+                  [&](const SolveCall& o) {
+                    return hdd_operator_solve_batched(ctx, o.mesh, o.pat, o.vals, o.n_comp, o.theta, range, d_b, ldb, d_x, ldx, n_rhs, o.opt,
+                                                      o.work, o.n_work, nullptr, 0, o.infos, stream);
+                  },
+                  [&](int32_t j) { return " for right-hand side " + std::to_string(j) + " of " + std::to_string(n_rhs); });
   }
   std::vector<std::vector<double>> apply_inverse(const std::vector<std::vector<double>>& b, double mu = 0.0,
                                                  const SolverOptions& options = SolverOptions(),
                                                  const hdd_block_range* range = nullptr,
                                                  std::vector<hdd_solve_info>* infos = nullptr) const
   {
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
     if (b.empty() || b.size() > size_t(HDD_MAX_VEC))
       throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC right-hand sides expected");
-    for (const auto& bj : b)
-      if (int64_t(bj.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
-    const int64_t ld = std::max<int64_t>(rows + (rows & 1), 2);
-    internal::DeviceArray<double> db{size_t(ld) * b.size()}, dx{size_t(ld) * b.size()};
-    for (size_t j = 0; j < b.size(); ++j)
-      if (rows)
-        internal::hip_check(hipMemcpy(db.get() + j * size_t(ld), b[j].data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice),
-                            "apply_inverse");
-    const auto i = apply_inverse(db.get(), ld, dx.get(), ld, int32_t(b.size()), mu, options, range);
-    if (infos) *infos = i;
-    const auto all = dx.download();
-    std::vector<std::vector<double>> x(b.size());
-    for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
-    return x;
+    return on_columns(b, rows_of(range), infos, [&](const double* d_b, double* d_x, int64_t ld) {
+      return apply_inverse(d_b, ld, d_x, ld, int32_t(b.size()), mu, options, range);
+    });
   }
   // x_j = A(mu_j)^-1 b_j for 1..HDD_MAX_VEC parameters at once (hdd_operator_solve_multi: pyMOR's apply_inverse(V,
   // mu=mu_j) over a parameter sample): d_b [mus.size()][ldb], d_x [mus.size()][ldx] device arrays.  Column j is bit
@@ -803,52 +772,27 @@ class AffinelyDecomposedMatrix {
   {
     const int32_t n_rhs = int32_t(mus.size());
     if (mus.empty() || mus.size() > size_t(HDD_MAX_VEC)) throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC parameters expected");
-    std::vector<const double*> v;
-    std::vector<double> thetas, theta;
-    for (const double mu : mus) {
-      v.clear();
-      theta.clear();
-      operands(mu, v, theta);
-      thetas.insert(thetas.end(), theta.begin(), theta.end());
-    }
-    const hdd_csr pat = pattern->csr();
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
-    const hdd_solve_options opt = solve_options(options, x0);
-    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_multi_workspace(rows, opt.block_size, n_rhs), 1);
-    internal::DeviceArray<double> work{size_t(n_work)};
-    std::vector<hdd_solve_info> infos(size_t(n_rhs), hdd_solve_info{});
-    internal::check(hdd_operator_solve_multi(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()),
-                                             thetas.data(), int64_t(v.size()), range, d_b, ldb, d_x, ldx, n_rhs, &opt, work.get(),
-                                             n_work, nullptr, 0, infos.data(), stream),
-                    "hdd_operator_solve_multi");
-    for (int32_t j = 0; j < n_rhs; ++j)
-      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
-        throw Stuff::Exceptions::linear_solver_failed(solver_failed(
-            infos[size_t(j)], " for column " + std::to_string(j) + " of " + std::to_string(n_rhs) + " (mu = " + std::to_string(mus[size_t(j)]) + ")"));
-    return infos;
+    const int64_t rows = rows_of(range);
+    return solved("hdd_operator_solve_multi", mus, n_rhs, options, x0,
+                  [&](int32_t bs) { return hdd_operator_solve_multi_workspace(rows, bs, n_rhs); },
+                  [&](const SolveCall& o) {
+                    return hdd_operator_solve_multi(ctx, o.mesh, o.pat, o.vals, o.n_comp, o.theta, int64_t(o.n_comp), range, d_b, ldb, d_x, ldx,
+                                                    n_rhs, o.opt, o.work, o.n_work, nullptr, 0, o.infos, stream);
+                  },
+                  [&](int32_t j) {
+                    return " for column " + std::to_string(j) + " of " + std::to_string(n_rhs) + " (mu = " + std::to_string(mus[size_t(j)]) + ")";
+                  });
   }
   std::vector<std::vector<double>> apply_inverse(const std::vector<std::vector<double>>& b, const std::vector<double>& mus,
                                                  const SolverOptions& options = SolverOptions(),
                                                  const hdd_block_range* range = nullptr,
                                                  std::vector<hdd_solve_info>* infos = nullptr) const
   {
-    const int64_t rows = range ? range->row_end - range->row_begin : pattern->rows;
     if (b.empty() || b.size() > size_t(HDD_MAX_VEC) || b.size() != mus.size())
       throw Stuff::Exceptions::wrong_input_given("apply_inverse: 1..HDD_MAX_VEC right-hand sides and a mu for each expected");
-    for (const auto& bj : b)
-      if (int64_t(bj.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
-    const int64_t ld = std::max<int64_t>(rows + (rows & 1), 2);
-    internal::DeviceArray<double> db{size_t(ld) * b.size()}, dx{size_t(ld) * b.size()};
-    for (size_t j = 0; j < b.size(); ++j)
-      if (rows)
-        internal::hip_check(hipMemcpy(db.get() + j * size_t(ld), b[j].data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice),
-                            "apply_inverse");
-    const auto i = apply_inverse(db.get(), ld, dx.get(), ld, mus, options, range);
-    if (infos) *infos = i;
-    const auto all = dx.download();
-    std::vector<std::vector<double>> x(b.size());
-    for (size_t j = 0; j < b.size(); ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
-    return x;
+    return on_columns(b, rows_of(range), infos, [&](const double* d_b, double* d_x, int64_t ld) {
+      return apply_inverse(d_b, ld, d_x, ld, mus, options, range);
+    });
   }
   // x_s = A_ss(mu)^-1 b_s for every segment s of a partition of a row interval in one device solve
   // (hdd_operator_solve_blocks): bounds [n + 1] are rows, strictly ascending; d_b, d_x: device [bounds[n] - bounds[0]],
@@ -862,39 +806,30 @@ class AffinelyDecomposedMatrix {
     if (bounds.size() < 2 || bounds.size() > size_t(HDD_MAX_SOLVE_BLOCKS) + 1)
       throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
     const int32_t n = int32_t(bounds.size()) - 1;
-    std::vector<const double*> v;
-    std::vector<double> theta;
-    operands(mu, v, theta);
-    const hdd_csr pat = pattern->csr();
     const int64_t rows = bounds.back() - bounds.front();
-    const hdd_solve_options opt = solve_options(options, x0);
-    const int64_t n_work = std::max<int64_t>(hdd_operator_solve_blocks_workspace(std::max<int64_t>(rows, 0), opt.block_size, n), 1);
-    internal::DeviceArray<double> work{size_t(n_work)};
-    std::vector<hdd_solve_info> infos(size_t(n), hdd_solve_info{});
-    internal::check(hdd_operator_solve_blocks(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()), theta.data(),
-                                              n, bounds.data(), d_b, d_x, &opt, work.get(), n_work, nullptr, 0, infos.data(), stream),
-                    "hdd_operator_solve_blocks");
-    for (int32_t j = 0; j < n; ++j)
-      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
-        throw Stuff::Exceptions::linear_solver_failed(solver_failed(
-            infos[size_t(j)], " for segment " + std::to_string(j) + " of " + std::to_string(n) + " (rows " +
-                                  std::to_string(bounds[size_t(j)]) + " .. " + std::to_string(bounds[size_t(j) + 1]) + ")"));
-    return infos;
+    return solved("hdd_operator_solve_blocks", {mu}, n, options, x0,
+                  [&](int32_t bs) { return hdd_operator_solve_blocks_workspace(std::max<int64_t>(rows, 0), bs, n); },
+                  [&](const SolveCall& o) {
+                    return hdd_operator_solve_blocks(ctx, o.mesh, o.pat, o.vals, o.n_comp, o.theta, n, bounds.data(), d_b, d_x, o.opt, o.work,
+                                                     o.n_work, nullptr, 0, o.infos, stream);
+                  },
+                  [&](int32_t j) {
+                    return " for segment " + std::to_string(j) + " of " + std::to_string(n) + " (rows " + std::to_string(bounds[size_t(j)]) +
+                           " .. " + std::to_string(bounds[size_t(j) + 1]) + ")";
+                  });
   }
   std::vector<double> apply_inverse_blocks(const std::vector<int64_t>& bounds, const std::vector<double>& b, double mu = 0.0,
                                            const SolverOptions& options = SolverOptions(),
                                            std::vector<hdd_solve_info>* infos = nullptr) const
   {
     if (bounds.size() < 2) throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: 1..HDD_MAX_SOLVE_BLOCKS segments expected");
-    const int64_t rows = bounds.back() - bounds.front();
+    const int64_t rows = bounds.back() - bounds.front(), ld = std::max<int64_t>(rows, 1);
     if (int64_t(b.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse_blocks: b has the wrong size");
-    internal::DeviceArray<double> db{size_t(std::max<int64_t>(rows, 1))}, dx{size_t(std::max<int64_t>(rows, 1))};
-    if (rows) internal::hip_check(hipMemcpy(db.get(), b.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_inverse_blocks");
+    const auto db = upload_columns(1, rows, ld, "apply_inverse_blocks", [&](size_t) { return b.data(); });
+    internal::DeviceArray<double> dx{size_t(ld)};
     const auto i = apply_inverse_blocks(bounds, db.get(), dx.get(), mu, options);
     if (infos) *infos = i;
-    auto x = dx.download();
-    x.resize(size_t(rows));
-    return x;
+    return download_first(dx, rows);
   }
   // y_s = A_ss(mu) x_s for every segment in one launch (hdd_operator_apply_blocks); asynchronous on `stream`
   void apply_blocks(const std::vector<int64_t>& bounds, const double* d_x, double* d_y, double mu = 0.0, void* stream = nullptr) const
@@ -918,9 +853,7 @@ class AffinelyDecomposedMatrix {
     if (rows) internal::hip_check(hipMemcpy(dx.get(), x.data(), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), "apply_blocks");
     apply_blocks(bounds, dx.get(), dy.get(), mu);
     internal::hip_check(hipDeviceSynchronize(), "apply_blocks");
-    auto y = dy.download();
-    y.resize(size_t(rows));
-    return y;
+    return download_first(dy, rows);
   }
   // The mesh whose SWIPDG face pattern `pattern` is, for hdd_operator_apply's tile kernel: a copy of the face
   // neighbours the matrix keeps alive itself (4 bytes per element face; the value arrays take 36 to 80 times that).
@@ -956,11 +889,77 @@ class AffinelyDecomposedMatrix {
            ", status " + std::to_string(info.status) + ") after " + std::to_string(info.iterations) + " iterations, residual " +
            std::to_string(info.residual) + ", ||b|| " + std::to_string(info.rhs_norm);
   }
-  std::vector<double> trimmed(const internal::DeviceArray<double>& a) const
+  std::vector<double> trimmed(const internal::DeviceArray<double>& a) const { return download_first(a, pattern->nnz); }
+  static std::vector<double> download_first(const internal::DeviceArray<double>& a, int64_t n)
   {
     auto h = a.download();
-    h.resize(size_t(pattern->nnz));
+    h.resize(size_t(n));
     return h;
+  }
+  int64_t rows_of(const hdd_block_range* range) const { return range ? range->row_end - range->row_begin : pattern->rows; }
+  // what solved() hands to the ABI call of an entry; theta is [mus.size()][n_comp]
+  struct SolveCall {
+    const hdd_mesh* mesh; const hdd_csr* pat; const double* const* vals; int32_t n_comp; const double* theta;
+    const hdd_solve_options* opt; double* work; int64_t n_work; hdd_solve_info* infos;
+  };
+  // Every device apply_inverse between "d_b, d_x are there" and "the n infos are filled": the operands at every mu, the
+  // pattern, the options, a workspace of workspace(block_size) doubles; call(SolveCall) is the ABI call `what`; the first
+  // info that did not converge throws linear_solver_failed, naming it by which(j)
+  template <class Workspace, class Call, class Which>
+  std::vector<hdd_solve_info> solved(const char* what, const std::vector<double>& mus, int32_t n, const SolverOptions& options, bool x0,
+                                     Workspace&& workspace, Call&& call, Which&& which) const
+  {
+    std::vector<const double*> v;
+    std::vector<double> thetas, theta;
+    for (const double mu : mus) {
+      v.clear();
+      theta.clear();
+      operands(mu, v, theta);
+      thetas.insert(thetas.end(), theta.begin(), theta.end());
+    }
+    const hdd_csr pat = pattern->csr();
+    const hdd_solve_options opt = solve_options(options, x0);
+    const int64_t n_work = std::max<int64_t>(workspace(opt.block_size), 1);
+    internal::DeviceArray<double> work{size_t(n_work)};
+    std::vector<hdd_solve_info> infos(size_t(n), hdd_solve_info{});
+    internal::check(call(SolveCall{tile_nbrs ? &tile_mesh : nullptr, &pat, v.data(), int32_t(v.size()), thetas.data(), &opt, work.get(),
+                                   n_work, infos.data()}),
+                    what);
+    for (int32_t j = 0; j < n; ++j)
+      if (infos[size_t(j)].status != HDD_SOLVE_CONVERGED)
+        throw Stuff::Exceptions::linear_solver_failed(solver_failed(infos[size_t(j)], which(j)));
+    return infos;
+  }
+  // n host columns (column(j): `rows` doubles) at leading dimension ld on the device, a failed copy reported as what's
+  template <class Column>
+  static internal::DeviceArray<double> upload_columns(size_t n, int64_t rows, int64_t ld, const char* what, Column&& column)
+  {
+    internal::DeviceArray<double> d{size_t(ld) * n};
+    for (size_t j = 0; j < n && rows; ++j)
+      internal::hip_check(hipMemcpy(d.get() + j * size_t(ld), column(j), size_t(rows) * sizeof(double), hipMemcpyHostToDevice), what);
+    return d;
+  }
+  // ... and back: the first `rows` of each of the n columns
+  static std::vector<std::vector<double>> download_columns(const internal::DeviceArray<double>& d, size_t n, int64_t rows, int64_t ld)
+  {
+    const auto all = d.download();
+    std::vector<std::vector<double>> x(n);
+    for (size_t j = 0; j < n; ++j) x[j].assign(all.begin() + int64_t(j) * ld, all.begin() + int64_t(j) * ld + rows);
+    return x;
+  }
+  // the host-vector apply_inverse on several columns: b on the device at an even leading dimension, solve(d_b, d_x, ld), x back
+  template <class Solve>
+  std::vector<std::vector<double>> on_columns(const std::vector<std::vector<double>>& b, int64_t rows, std::vector<hdd_solve_info>* infos,
+                                              Solve&& solve) const
+  {
+    for (const auto& bj : b)
+      if (int64_t(bj.size()) != rows) throw Stuff::Exceptions::wrong_input_given("apply_inverse: b has the wrong size");
+    const int64_t ld = std::max<int64_t>(rows + (rows & 1), 2);
+    const auto db = upload_columns(b.size(), rows, ld, "apply_inverse", [&](size_t j) { return b[j].data(); });
+    internal::DeviceArray<double> dx{size_t(ld) * b.size()};
+    const auto i = solve(db.get(), dx.get(), ld);
+    if (infos) *infos = i;
+    return download_columns(dx, b.size(), rows, ld);
   }
 };
 
