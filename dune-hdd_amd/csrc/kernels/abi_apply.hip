@@ -110,6 +110,13 @@ void hdd::abi::apply_kernel_name(std::string& out, const ApplyPlan& P, bool per_
   out += dot ? ", dot>" : ">";
 }
 
+void hdd::abi::name_project_kernel(const ApplyPlan& P)
+{
+  std::string& out = last_apply_kernel_slot();
+  out = P.tile ? "project_tile_kernel<" : "project_csr_kernel<";
+  out += P.tile ? (P.nb == 3 ? "3, 3>" : "4, 4>") : (P.short_rows ? "8>" : "64>");
+}
+
 int hdd::abi::run_apply(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const ApplyThetas* T, const double* d_x, int64_t ldx,
                         double* d_y, int64_t ldy, int32_t n_vec, void* stream)
 {

@@ -51,6 +51,10 @@ int run_apply(const char* who, hdd_ctx* ctx, const ApplyPlan& P, const ApplyThet
 // takes for the plan, appended to out
 void apply_kernel_name(std::string& out, const ApplyPlan& P, bool per_vector, int nv, bool dot);
 
+// hdd_operator_project (abi_project.hip): names the plan's "project_tile_kernel<3, 3>", "project_csr_kernel<8>", ...
+// as this thread's last apply kernel
+void name_project_kernel(const ApplyPlan& P);
+
 // Workgroups of a plain launch.  Tile kernel: as many waves per CU as LDS images fit (8 P1, 4 Q1 of the 160 KB),
 // tile_range wants a multiple of 8 workgroups; CSR kernel: 256 / G rows per workgroup pass.
 inline int64_t apply_grid(const hdd_ctx* ctx, const ApplyPlan& P)

@@ -103,6 +103,7 @@ class BlockRange(C.Structure):
 
 
 MAX_VEC = 8
+MAX_BASIS = 64
 MAX_SOLVE_BLOCKS = 4096
 PRECOND_NONE, PRECOND_BLOCK_JACOBI = 0, 1
 SOLVE_CONVERGED, SOLVE_MAX_ITER, SOLVE_BREAKDOWN = 0, 1, 2
@@ -238,6 +239,9 @@ def lib():
         "hdd_operator_apply2": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _I64, _I32, _VP, _I64, _I32, _VP, _I64,
                                        _VP, _VP]),
         "hdd_last_apply_kernel": (C.c_char_p, []),
+        "hdd_operator_project_workspace": (_I64, [_I32, _I32, _I32]),
+        "hdd_operator_project": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _I64, _I32, _VP, _I64, _I32, _VP, _I64, _VP, _VP]),
+        "hdd_vectors_inner": (_I32, [_VP, _VP, _I64, _I32, _VP, _I64, _I32, _I64, _VP, _I64, _VP, _VP]),
         "hdd_operator_solve_workspace": (_I64, [_I64, _I32]),
         "hdd_operator_solve": (_I32, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _VP, _I64, _VP, _VP, _VP]),
         "hdd_last_solve_kernels": (C.c_char_p, []),
@@ -975,6 +979,63 @@ def apply2(ctx, dpattern, vals, v, u, theta=None, dmesh=None, block=None, stream
                                      v2.stride(0) if n_v > 1 else max(rows, 1), n_v, u2.data_ptr(),
                                      u2.stride(0) if n_u > 1 else max(cols, 1), n_u, work.data_ptr(), work.stride(0),
                                      out.data_ptr(), C.c_void_p(s)), "hdd_operator_apply2")
+    return out
+
+
+def project_workspace(n_comp, n_v, n_u):
+    """hdd_operator_project_workspace: doubles of workspace of project (and, with n_comp = 1, of inner); 0 for sizes
+    the calls reject"""
+    return int(lib().hdd_operator_project_workspace(n_comp, n_v, n_u))
+
+
+def _basis(who, what, t, m):
+    """a basis as [k, m] float64 with unit inner stride (a 1-d tensor counts as one vector) and its leading dimension"""
+    torch = _torch()
+    t2 = t if t.dim() == 2 else t.reshape(1, -1)
+    if t2.dtype != torch.float64 or t2.stride(1) != 1 or t2.shape[1] != m:
+        raise HddError("%s: %s must be float64 [k, %d] with unit inner stride" % (who, what, m))
+    if not 1 <= t2.shape[0] <= MAX_BASIS:
+        raise HddError("%s: 1..%d vectors in %s" % (who, MAX_BASIS, what))
+    return t2, (t2.stride(0) if t2.shape[0] > 1 else max(m, 1))
+
+
+def project(ctx, dpattern, vals, V, U=None, dmesh=None, block=None, out=None, stream=None, grid=None):
+    """hdd_operator_project: the [n_comp, n_v, n_u] tensor G[q, i, j] = V[i]^T A_q U[j], A_q = vals[q] on dpattern --
+    every affine component projected onto a reduced basis in one pass over the values (no theta: A(mu) reduced is a
+    lincomb of the small matrices).  V: [n_v, rows] (or [rows]), U: [n_u, cols] (None: U = V), up to MAX_BASIS vectors
+    each, rows may be strided.  dmesh / block / grid as in apply().  Entry (q, i, j) does not depend on the other
+    vectors or on the basis sizes: extending a basis needs only the new row and column."""
+    torch = _torch()
+    vals, n, ptrs, _, rng, rows, cols, dmesh = _apply_operands(dpattern, vals, None, dmesh, block, grid)
+    v2, ldv = _basis("project", "V", V, rows)
+    u2, ldu = _basis("project", "U", V if U is None else U, cols)
+    n_v, n_u = v2.shape[0], u2.shape[0]
+    work = torch.empty(project_workspace(n, n_v, n_u), dtype=torch.float64, device=v2.device)
+    if out is None:
+        out = torch.empty((n, n_v, n_u), dtype=torch.float64, device=v2.device)
+    if out.dtype != torch.float64 or out.shape != (n, n_v, n_u) or not out.is_contiguous():
+        raise HddError("project: out must be contiguous float64 [%d, %d, %d]" % (n, n_v, n_u))
+    s = stream if stream is not None else torch.cuda.current_stream(v2.device).cuda_stream
+    _check(lib().hdd_operator_project(ctx.h, None if dmesh is None else C.addressof(dmesh.t), C.addressof(dpattern.t), ptrs,
+                                      n, None if rng is None else C.addressof(rng), v2.data_ptr(), ldv, n_v,
+                                      u2.data_ptr(), ldu, n_u, work.data_ptr(), work.numel(), out.data_ptr(),
+                                      C.c_void_p(s)), "hdd_operator_project")
+    return out
+
+
+def inner(ctx, V, W, stream=None):
+    """hdd_vectors_inner: the [n_v, n_w] tensor V[i] . W[j] -- reduced right-hand sides V^T b_q, functionals, a
+    Euclidean Gramian.  V: [n_v, n] (or [n]), W: [n_w, n] (or [n]), up to MAX_BASIS vectors each."""
+    torch = _torch()
+    m = V.shape[-1]
+    v2, ldv = _basis("inner", "V", V, m)
+    w2, ldw = _basis("inner", "W", W, m)
+    n_v, n_w = v2.shape[0], w2.shape[0]
+    work = torch.empty(project_workspace(1, n_v, n_w), dtype=torch.float64, device=v2.device)
+    out = torch.empty((n_v, n_w), dtype=torch.float64, device=v2.device)
+    s = stream if stream is not None else torch.cuda.current_stream(v2.device).cuda_stream
+    _check(lib().hdd_vectors_inner(ctx.h, v2.data_ptr(), ldv, n_v, w2.data_ptr(), ldw, n_w, m, work.data_ptr(),
+                                   work.numel(), out.data_ptr(), C.c_void_p(s)), "hdd_vectors_inner")
     return out
 
 

@@ -483,9 +483,49 @@ int hdd_operator_apply2(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* patte
                         int32_t n_comp, const double* theta, const hdd_block_range* range, const double* d_v,
                         int64_t ldv, int32_t n_v, const double* d_u, int64_t ldu, int32_t n_u, double* d_work,
                         int64_t ldw, double* d_out, void* stream);
-/* the kernel the last hdd_operator_apply / _apply2 of this thread launched ("" if none), like hdd_last_tile_kernel:
- * "apply_tile_kernel<NB, NF, NV>" or "apply_csr_kernel<G, NV>" */
+/* the kernel the last hdd_operator_apply / _apply2 / _project of this thread launched ("" if none), like
+ * hdd_last_tile_kernel: "apply_tile_kernel<NB, NF, NV>" or "apply_csr_kernel<G, NV>" ("project_tile_kernel<NB, NF>",
+ * "project_csr_kernel<G>") */
 const char* hdd_last_apply_kernel(void);
+
+/* ---------------------------------------------------------------------------------------------- */
+/* reduced-basis projection -- every affine component onto a basis in one pass over the values:     */
+/* G_q = V^T A_q U, the reduced right-hand sides V^T b_q, a product's Gramian.  Additive to ABI 8.   */
+/* ---------------------------------------------------------------------------------------------- */
+#define HDD_MAX_BASIS 64
+/* doubles of workspace; a function of its arguments alone; 0 for arguments the call would reject.  The calls below
+ * leave at most 512 partial sums per entry there: 512 * n_comp * n_v * n_u doubles -- 8 MiB for two components on a
+ * 32 x 32 basis, 128 MiB at n_comp = 8, 64 x 64. */
+int64_t hdd_operator_project_workspace(int32_t n_comp, int32_t n_v, int32_t n_u);
+/* d_out[(q*n_v + i)*n_u + j] = v_i^T A_q u_j on the (restricted) operator; q < n_comp, i < n_v, j < n_u, n_v and n_u
+ * in 1..HDD_MAX_BASIS.  No theta: the components come out separately, A(mu) reduced is a host lincomb of small
+ * matrices.  mesh / pattern / d_vals / range follow hdd_operator_apply's rules: the operator (ss, nn) of a BlockSWIPDG
+ * is projected in place through `range` (v in ss's numbering, u in nn's); entries outside the column range are
+ * skipped, not multiplied by zero, and neither they nor the padding behind ldv / ldu are read.  d_v is [n_v][ldv]
+ * (ldv >= rows), d_u [n_u][ldu] (ldu >= columns), d_work the caller's n_work >=
+ * hdd_operator_project_workspace(n_comp, n_v, n_u) doubles, d_out device [n_comp*n_v*n_u].
+ * W = A_q U is never written: a wave forms it for a panel of 16 u-vectors on its rows and contracts it at once with
+ * the same rows of V on the f64 matrix cores; every workgroup leaves its share in d_work and a second kernel adds
+ * the workgroups in order.  The mesh of a 2d P1 / Q1 whole-grid face pattern with an nb-aligned range selects the
+ * tile kernel (hdd_last_apply_kernel(): "project_tile_kernel<3, 3>" / "<4, 4>"), everything else the CSR kernel
+ * ("project_csr_kernel<8>" / "<64>"), as for hdd_operator_apply.
+ * Asynchronous on `stream`; allocates nothing, synchronises nothing, uses no atomics: bit-identical from call to call.
+ * On a given path entry (q, i, j) is a function of A_q, v_i, u_j and the range alone -- not of n_v, n_u, the other
+ * vectors or the position of v_i / u_j in the call: a basis extended by one vector needs only the new row and column,
+ * which are bit for bit those of the full re-projection.
+ * Every argument check precedes the first device call: HDD_ERR_INVALID for a null pointer, n_comp outside
+ * 1..HDD_MAX_COMP, n_v / n_u outside 1..HDD_MAX_BASIS, ldv / ldu too small, n_work below the workspace function's
+ * value, a range outside the matrix, a mesh that does not match the pattern's rows. */
+int hdd_operator_project(hdd_ctx* ctx, const hdd_mesh* mesh, const hdd_csr* pattern, const double* const* d_vals,
+                         int32_t n_comp, const hdd_block_range* range, const double* d_v, int64_t ldv, int32_t n_v,
+                         const double* d_u, int64_t ldu, int32_t n_u, double* d_work, int64_t n_work, double* d_out,
+                         void* stream);
+/* d_out[i*n_w + j] = v_i . w_j over n entries, n_v and n_w in 1..HDD_MAX_BASIS: reduced right-hand sides V^T b_q,
+ * functionals, a Euclidean Gramian.  d_v is [n_v][ldv], d_w [n_w][ldw] (ldv, ldw >= n), d_work the caller's n_work >=
+ * hdd_operator_project_workspace(1, n_v, n_w) doubles.  The same two stages and the same guarantees as
+ * hdd_operator_project. */
+int hdd_vectors_inner(hdd_ctx* ctx, const double* d_v, int64_t ldv, int32_t n_v, const double* d_w, int64_t ldw,
+                      int32_t n_w, int64_t n, double* d_work, int64_t n_work, double* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* solve -- the apply_inverse of ContainerBasedDefault::uncached_solve (base.hh:327-367) on the      */

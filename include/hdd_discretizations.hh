@@ -705,6 +705,69 @@ class AffinelyDecomposedMatrix {
     internal::hip_check(hipDeviceSynchronize(), "apply2");
     return out.download()[0];
   }
+  // G_q = V^T A_q U for every value array at once (hdd_operator_project): the reduced operator components of a
+  // reduced-basis projection, in the order of A(mu)'s terms -- the affine part first where there is one, then the
+  // components -- each a row-major [n_v][n_u] matrix; A(mu) reduced is their lincomb with (1, theta_q(mu)).  d_v
+  // [n_v][ldv], d_u [n_u][ldu] device arrays of 1..HDD_MAX_BASIS vectors (ldv >= rows, ldu >= columns of the --
+  // restricted -- operator).  Entry (q, i, j) depends on A_q, v_i, u_j alone: after a basis extension only the new
+  // row and column need computing.  Synchronises `stream`.
+  std::vector<std::vector<double>> project(const double* d_v, int64_t ldv, int32_t n_v, const double* d_u, int64_t ldu, int32_t n_u,
+                                           const hdd_block_range* range = nullptr, void* stream = nullptr) const
+  {
+    std::vector<const double*> a;
+    if (affine) a.push_back(affine->get());
+    for (const auto& c : comps) a.push_back(c->get());
+    if (a.empty() || a.size() > HDD_MAX_COMP) throw Stuff::Exceptions::wrong_input_given("project: 1..HDD_MAX_COMP value arrays expected");
+    const int64_t n_work = hdd_operator_project_workspace(int32_t(a.size()), n_v, n_u);
+    if (n_work == 0) throw Stuff::Exceptions::wrong_input_given("project: 1..HDD_MAX_BASIS vectors expected");
+    const size_t each = size_t(n_v) * size_t(n_u);
+    internal::DeviceArray<double> work{size_t(n_work)}, out{a.size() * each};
+    const hdd_csr pat = pattern->csr();
+    internal::check(hdd_operator_project(ctx, tile_nbrs ? &tile_mesh : nullptr, &pat, a.data(), int32_t(a.size()), range, d_v, ldv, n_v,
+                                         d_u, ldu, n_u, work.get(), n_work, out.get(), stream),
+                    "hdd_operator_project");
+    internal::hip_check(hipStreamSynchronize(static_cast<hipStream_t>(stream)), "project");
+    const auto all = out.download();
+    std::vector<std::vector<double>> G(a.size());
+    for (size_t q = 0; q < a.size(); ++q) G[q].assign(all.begin() + int64_t(q * each), all.begin() + int64_t((q + 1) * each));
+    return G;
+  }
+  // ... of host vectors: V of `rows`, U of `columns` entries each
+  std::vector<std::vector<double>> project(const std::vector<std::vector<double>>& V, const std::vector<std::vector<double>>& U,
+                                           const hdd_block_range* range = nullptr) const
+  {
+    const int64_t rows = rows_of(range), cols = range ? range->col_end - range->col_begin : pattern->cols;
+    if (V.empty() || V.size() > size_t(HDD_MAX_BASIS) || U.empty() || U.size() > size_t(HDD_MAX_BASIS))
+      throw Stuff::Exceptions::wrong_input_given("project: 1..HDD_MAX_BASIS vectors expected");
+    for (const auto& v : V)
+      if (int64_t(v.size()) != rows) throw Stuff::Exceptions::wrong_input_given("project: a vector of V has the wrong size");
+    for (const auto& u : U)
+      if (int64_t(u.size()) != cols) throw Stuff::Exceptions::wrong_input_given("project: a vector of U has the wrong size");
+    const int64_t ldv = std::max<int64_t>(rows, 1), ldu = std::max<int64_t>(cols, 1);
+    const auto dv = upload_columns(V.size(), rows, ldv, "project", [&](size_t j) { return V[j].data(); });
+    const auto du = upload_columns(U.size(), cols, ldu, "project", [&](size_t j) { return U[j].data(); });
+    return project(dv.get(), ldv, int32_t(V.size()), du.get(), ldu, int32_t(U.size()), range);
+  }
+  // V^T W of host vectors of equal size (hdd_vectors_inner), row-major [V.size()][W.size()]: reduced right-hand
+  // sides, functionals, a Euclidean Gramian
+  std::vector<double> inner(const std::vector<std::vector<double>>& V, const std::vector<std::vector<double>>& W) const
+  {
+    if (V.empty() || V.size() > size_t(HDD_MAX_BASIS) || W.empty() || W.size() > size_t(HDD_MAX_BASIS))
+      throw Stuff::Exceptions::wrong_input_given("inner: 1..HDD_MAX_BASIS vectors expected");
+    const int64_t n = int64_t(V[0].size()), ld = std::max<int64_t>(n, 1);
+    for (const auto* S : {&V, &W})
+      for (const auto& v : *S)
+        if (int64_t(v.size()) != n) throw Stuff::Exceptions::wrong_input_given("inner: the vectors differ in size");
+    const auto dv = upload_columns(V.size(), n, ld, "inner", [&](size_t j) { return V[j].data(); });
+    const auto dw = upload_columns(W.size(), n, ld, "inner", [&](size_t j) { return W[j].data(); });
+    const int64_t n_work = hdd_operator_project_workspace(1, int32_t(V.size()), int32_t(W.size()));
+    internal::DeviceArray<double> work{size_t(n_work)}, out{V.size() * W.size()};
+    internal::check(hdd_vectors_inner(ctx, dv.get(), ld, int32_t(V.size()), dw.get(), ld, int32_t(W.size()), n, work.get(), n_work,
+                                      out.get(), nullptr),
+                    "hdd_vectors_inner");
+    internal::hip_check(hipDeviceSynchronize(), "inner");
+    return download_first(out, int64_t(V.size() * W.size()));
+  }
   using SolverOptions = Discretizations::SolverOptions;
   // x = A(mu)^-1 b: what uncached_solve does with the container (base.hh:327-367: lincomb, then apply_inverse), by
   // hdd_operator_solve -- A(mu) is never written, theta is fused into the iteration's applies.  A(mu) must be
@@ -996,6 +1059,57 @@ class AffinelyDecomposedVector {
   }
 };
 
+// What SWIPDG::project leaves of the discretization on a basis of n vectors: the reduced operator and right-hand side
+// terms (the affine part first where there is one, then the components with their coefficients) and the reduced
+// solve on the host.  operators[k] is row-major [n][n], rhs[k] has n entries.
+struct ReducedProblem {
+  int n = 0;
+  bool has_affine_operator = false, has_affine_rhs = false;
+  std::vector<std::vector<double>> operators, rhs;
+  std::vector<Pymor::ParameterFunctional> operator_coefficients, rhs_coefficients;
+
+  // sum_k theta_k(mu) terms[k], the affine part at 1
+  static std::vector<double> lincomb(const std::vector<std::vector<double>>& terms, bool affine,
+                                     const std::vector<Pymor::ParameterFunctional>& coefficients, double mu, size_t size)
+  {
+    std::vector<double> out(size, 0.0);
+    for (size_t k = 0; k < terms.size(); ++k) {
+      const double th = affine && k == 0 ? 1.0 : coefficients.at(k - (affine ? 1 : 0)).evaluate(mu);
+      for (size_t i = 0; i < size; ++i) out[i] += th * terms[k][i];
+    }
+    return out;
+  }
+  std::vector<double> operator_at(double mu) const { return lincomb(operators, has_affine_operator, operator_coefficients, mu, size_t(n) * size_t(n)); }
+  std::vector<double> rhs_at(double mu) const { return lincomb(rhs, has_affine_rhs, rhs_coefficients, mu, size_t(n)); }
+  // the reduced coefficients at mu: A_N(mu) c = b_N(mu) by a dense Cholesky factorisation (A_N(mu) is symmetric positive
+  // definite where A(mu) is and the basis is linearly independent)
+  std::vector<double> solve(double mu) const
+  {
+    std::vector<double> L = operator_at(mu), c = rhs_at(mu);
+    const size_t N = size_t(n);
+    for (size_t j = 0; j < N; ++j) {
+      double d = L[j * N + j];
+      for (size_t k = 0; k < j; ++k) d -= L[j * N + k] * L[j * N + k];
+      if (!(d > 0.0)) throw Stuff::Exceptions::linear_solver_failed("ReducedProblem::solve: the reduced operator is not positive definite");
+      L[j * N + j] = std::sqrt(d);
+      for (size_t i = j + 1; i < N; ++i) {
+        double s = L[i * N + j];
+        for (size_t k = 0; k < j; ++k) s -= L[i * N + k] * L[j * N + k];
+        L[i * N + j] = s / L[j * N + j];
+      }
+    }
+    for (size_t i = 0; i < N; ++i) {
+      for (size_t k = 0; k < i; ++k) c[i] -= L[i * N + k] * c[k];
+      c[i] /= L[i * N + i];
+    }
+    for (size_t i = N; i-- > 0;) {
+      for (size_t k = i + 1; k < N; ++k) c[i] -= L[k * N + i] * c[k];
+      c[i] /= L[i * N + i];
+    }
+    return c;
+  }
+};
+
 namespace detail {
 inline int degree_of(const hdd_grid_info& gi)
 {
@@ -1280,6 +1394,30 @@ class SWIPDG {
       bmus.push_back(std::move(bmu));
     }
     return system_matrix().apply_inverse(bmus, mus, options, nullptr, infos);
+  }
+
+  // The reduced-basis projection of the discretization onto `basis` (1..HDD_MAX_BASIS vectors of size() entries): every
+  // operator term in one pass over the value arrays (hdd_operator_project), every right-hand side term through
+  // hdd_vectors_inner.  ReducedProblem::solve(mu) then gives the coefficients of the reduced solution in the basis.
+  ReducedProblem project(const std::vector<std::vector<double>>& basis) const
+  {
+    const auto& A = system_matrix();
+    const auto& b = rhs();
+    ReducedProblem R;
+    R.n = int(basis.size());
+    R.operators = A.project(basis, basis);
+    R.has_affine_operator = A.has_affine_part();
+    R.operator_coefficients = A.coefficients;
+    std::vector<std::vector<double>> terms;
+    if (b.affine) terms.push_back(b.affine_part());
+    for (int q = 0; q < b.num_components(); ++q) terms.push_back(b.component(q));
+    if (!terms.empty()) {
+      const auto g = A.inner(terms, basis);   // [terms][n]
+      for (size_t k = 0; k < terms.size(); ++k) R.rhs.emplace_back(g.begin() + int64_t(k) * R.n, g.begin() + int64_t(k + 1) * R.n);
+    }
+    R.has_affine_rhs = bool(b.affine);
+    R.rhs_coefficients = b.coefficients;
+    return R;
   }
 
   // base.hh:272-291: only the products requested in the ctor (only_these_products, swipdg.hh:496-508)
@@ -1892,6 +2030,27 @@ class BlockSWIPDG : public SWIPDG {
     return apply_block(ss, nn, x, mu);
   }
 
+  // Vs^T A_q(ss, ss) Vs and Vs^T A_q(ss, nn) Vn for every component WITHOUT extracting the operators: LRBMS's reduced
+  // local and coupling operators through a block range (hdd_operator_project; AffinelyDecomposedMatrix::project says
+  // what comes back).  Vs in ss's local numbering, Vn in nn's.
+  std::vector<std::vector<double>> project_local(int ss, const std::vector<std::vector<double>>& Vs) const
+  {
+    range_check(ss);
+    const hdd_block_range rng = block_range(ss, ss);
+    return system_matrix().project(Vs, Vs, &rng);
+  }
+  std::vector<std::vector<double>> project_coupling(int ss, int nn, const std::vector<std::vector<double>>& Vs,
+                                                    const std::vector<std::vector<double>>& Vn) const
+  {
+    range_check(ss);
+    if (!neighbours_[size_t(ss)].count(nn))
+      throw Stuff::Exceptions::index_out_of_range("Subdomain " + std::to_string(nn) + " is not a neighbour of subdomain " +
+                                                  std::to_string(ss) + " (call neighbouring_subdomains(" +
+                                                  std::to_string(ss) + ") to find out)!");
+    const hdd_block_range rng = block_range(ss, nn);
+    return system_matrix().project(Vs, Vn, &rng);
+  }
+
   // The local solve get_local_operator(ss)^-1 b WITHOUT extracting the operator: the diagonal block of ss of the
   // global matrix through a block range (hdd_operator_solve; the diagonal block of an SPD matrix is SPD).  b and the
   // result in ss's local numbering.
@@ -2247,13 +2406,19 @@ class BlockSWIPDG : public SWIPDG {
                                                   " is not true for ss = " + std::to_string(ss) + "!");
   }
 
-  std::vector<double> apply_block(int ss, int nn, const std::vector<double>& x, double mu) const
+  // rows of ss, columns of nn of the global matrix
+  hdd_block_range block_range(int ss, int nn) const
   {
     int64_t a, b, c, d;
     internal::check(hdd_grid_subdomain_range(grid_, ss, ss + 1, &a, &b), "range");
     internal::check(hdd_grid_subdomain_range(grid_, nn, nn + 1, &c, &d), "range");
     const int64_t nb = info_.nb;
-    const hdd_block_range rng{a * nb, b * nb, c * nb, d * nb};
+    return hdd_block_range{a * nb, b * nb, c * nb, d * nb};
+  }
+
+  std::vector<double> apply_block(int ss, int nn, const std::vector<double>& x, double mu) const
+  {
+    const hdd_block_range rng = block_range(ss, nn);
     return system_matrix().apply(x, mu, &rng);
   }
 
